@@ -15,11 +15,17 @@ Other BASELINE configs, one JSON line each (``--workload``):
 Defaults follow SURVEY.md 8(d): M = 1000 timed sweeps after B = 100 burn-in sweeps, every
 timed sweep recording beta / lambda / sig2 / tau into the device-resident trace.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up (--warmup sweeps, then min(--steps, 20) settling sweeps: the ones
+--full runs as its per-phase split, so both time the same sweeps of the chain), times the
+--steps sweeps and prints ONE JSON line (rank 0) with the driver's contract fields (metric,
+value, unit, ms_per_step, ...).  ``--dump-outputs DIR``
+also writes the chain state the last timed sweep left (DIR/<name>.npy) for comparing two
+builds.  ``--full`` adds everything that takes runs of its own:
   roofline     -- the dominant kernel: algorithmic work per launch / average launch duration
-                  from HIP events on the engine stream
+                  from HIP events on the engine stream (with the per-phase split that picks it)
   cpu_baseline -- the oracle's sweep (numpy/scipy OpenBLAS + C latent sampler) timed on this
-                  host on a bounded number of sweeps (rank 0, N=1 only).
+                  host on a bounded number of sweeps (rank 0, N=1 only)
+  fitted_regime, reference_protocol, and for N > 1 the pre-timing parity_check.
 """
 from __future__ import annotations
 
@@ -550,6 +556,43 @@ def fail(msg, code=2):
     raise SystemExit(code)
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array of `arrays` as dirname/<name>.npy in float64.  When they
+    exceed `budget` bytes together, an array above its equal share is cut to a sample of its
+    (flattened) entries that fills the share: sorted indices drawn without replacement from
+    DATA_SEED and the array's size, the same in every run and build."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        share = budget // (8 * len(arrays))
+        for k, a in arrays.items():
+            if a.size > share:
+                idx = np.random.default_rng([DATA_SEED, a.size]).choice(a.size, size=share,
+                                                                        replace=False)
+                arrays[k] = a.ravel()[np.sort(idx)]
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def final_state(engines, dist=None):
+    """The chain state after the last sweep as a caller receives it: beta and lambda of every
+    column shard in column order (this process's engines, then gathered over the ranks), the
+    scalars from the first shard (they are replicated)."""
+    parts = [(e.cfg.j0, e.state()) for e in engines]
+    if dist:
+        gathered = [None] * dist.get_world_size()
+        dist.all_gather_object(gathered, parts)
+        parts = [x for g in gathered for x in g]
+    parts.sort(key=lambda q: q[0])
+    s0 = parts[0][1]
+    return {"beta": np.concatenate([s["beta"] for _, s in parts]),
+            "lambda": np.concatenate([s["lambda"] for _, s in parts]),
+            "sig2": s0["sig2"], "tau": s0["tau"], "alpha": s0["alpha"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -583,6 +626,14 @@ def main():
     ap.add_argument("--tuning", action="append", default=[], metavar="KEY=VALUE",
                     help="bb_set_tuning(KEY, VALUE) before the engines are built (A/B runs; "
                          "include/bayesbridge.h lists the keys)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed sweeps: the per-phase split and the dominant kernel's "
+                         "roofline, the fitted-regime and reference-protocol runs, the CPU "
+                         "baselines and (N > 1) the pre-timing parity check; the --no-*, "
+                         "--cpu-sweeps and --timing-stride options act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps write the chain state the last of them left "
+                         "(beta, lambda, sig2, tau, alpha) as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     wn, wp, walpha, kind = WORKLOADS[args.workload]
     n = args.rows or wn
@@ -714,8 +765,9 @@ def run_chain(args, n, p, alpha, kind, mode):
         if dist:
             dist.barrier()
 
+    full = args.full
     parity = None
-    if world > 1 and not args.no_parity_check:
+    if full and world > 1 and not args.no_parity_check:
         parity = shard_parity_check(bb, dist, rank, engines, my_ranks, runner, make_engine,
                                     devices[0], p, world)
         if not parity["ok"]:
@@ -729,30 +781,39 @@ def run_chain(args, n, p, alpha, kind, mode):
     runner.run(t, args.warmup, first_slot=-1)
     t += args.warmup
     sync_all()
-    # per-phase breakdown (untimed, an event at every phase start of rank 0's sweeps): it
-    # also picks the dominant single-kernel phase, whose launches the timed loop brackets
+    # up to 20 more untimed sweeps settle the device before the timed window; a plain run and a
+    # --full run time the same sweeps of the chain, so their values and dumps compare
     nph = max(1, min(args.steps, 20))
-    eng.enable_timing(True, phases=True)
-    eng.reset_timing()
-    ph0 = eng.nid_stats()
-    runner.run(t, nph, first_slot=-1)
-    t += nph
-    sync_all()
-    phases = eng.phase_times()
-    ph1 = eng.nid_stats()
-    # the phase-split sweeps took the near-identity path (their Gram phases are no-ops)
-    nid_phase_cheb = ph1["mode"] >= 0 and (ph1["cheb_sweeps"] - ph0["cheb_sweeps"]) * 2 > nph
-    _, sweep_ms_phases, _ = eng.kernel_times()
-    dom = max((ph for ph in SINGLE_KERNEL_PHASES if ph in phases), key=lambda k: phases[k])
+    if not full:
+        runner.run(t, nph, first_slot=-1)
+        t += nph
+        sync_all()
+    else:
+        # --full runs them as the per-phase breakdown (an event at every phase start of rank
+        # 0's sweeps): it also picks the dominant single-kernel phase, whose launches the timed
+        # loop brackets
+        eng.enable_timing(True, phases=True)
+        eng.reset_timing()
+        ph0 = eng.nid_stats()
+        runner.run(t, nph, first_slot=-1)
+        t += nph
+        sync_all()
+        phases = eng.phase_times()
+        ph1 = eng.nid_stats()
+        # the phase-split sweeps took the near-identity path (their Gram phases are no-ops)
+        nid_phase_cheb = ph1["mode"] >= 0 and (ph1["cheb_sweeps"] - ph0["cheb_sweeps"]) * 2 > nph
+        _, sweep_ms_phases, _ = eng.kernel_times()
+        dom = max((ph for ph in SINGLE_KERNEL_PHASES if ph in phases), key=lambda k: phases[k])
     barrier()
-    # every stride-th timed sweep brackets its dominant-phase launch (an event pair costs ~6 us
-    # of stream time per bracketed sweep: 1-2 % of a near-identity C3 sweep at stride 1); the
-    # E-apply's bytes per launch need every launch counted (pass_frac below)
-    stride = 1 if dom == "eapply" else max(1, args.timing_stride)
-    eng.enable_timing(True, phases=False, timed_phase=dom, stride=stride)
-    eng.reset_timing()
-    nid0 = eng.nid_stats()
-    mix0 = eng.nid_mixed()
+    if full:
+        # every stride-th timed sweep brackets its dominant-phase launch (an event pair costs
+        # ~6 us of stream time per bracketed sweep: 1-2 % of a near-identity C3 sweep at stride
+        # 1); the E-apply's bytes per launch need every launch counted (pass_frac below)
+        stride = 1 if dom == "eapply" else max(1, args.timing_stride)
+        eng.enable_timing(True, phases=False, timed_phase=dom, stride=stride)
+        eng.reset_timing()
+        nid0 = eng.nid_stats()
+        mix0 = eng.nid_mixed()
     t0 = time.perf_counter()
     # the timed loop records every sweep's beta / lambda / sig2 / tau into the device trace
     # ring, as the reference's MCMC loop writes its output slots (BridgeWrapper.cpp:287-298)
@@ -765,84 +826,109 @@ def run_chain(args, n, p, alpha, kind, mode):
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    dom_ms, _, _ = eng.kernel_times()
-    brackets = eng.timed_brackets()
-    # the exact kernel instances the timed sweeps launched (the PMC evidence is matched on them)
-    instances = {ph: bb.kernel_instance(ph) for ph in SINGLE_KERNEL_PHASES}
-    nid1 = eng.nid_stats()
-    mix1 = eng.nid_mixed()
-    eng.enable_timing(False)
-    nid = None
-    ctx_pass_frac = 1.0
-    ctx_pass32 = 0.0
-    if nid1["mode"] >= 0:
-        dc = nid1["cheb_sweeps"] - nid0["cheb_sweeps"]
-        dp = nid1["products"] - nid0["products"]
-        nid = {"timed_sweeps": args.steps, "chebyshev_sweeps": dc,
-               "cholesky_sweeps": nid1["chol_sweeps"] - nid0["chol_sweeps"],
-               "eapply_passes_per_chebyshev_sweep": (dp / dc) if dc else None,
-               "mixed_plan_sweeps": mix1["mixed_sweeps"] - mix0["mixed_sweeps"],
-               "fp32_passes_per_chebyshev_sweep": ((mix1["products32"] - mix0["products32"]) / dc
-                                                   if dc else None),
-               "eps_last": nid1["eps"],
-               "rule": "per sweep on the device: Chebyshev iteration on the certified spectrum "
-                       "interval [1, 1 + eps], eps >= lambda_max(X D X') / sig2 (the least of "
-                       "the trace and thresholded sums + T Lambda, Lambda >= lambda_max(X X') "
-                       "certified at setup), when K iterates (at most the cost model's cap) "
-                       "bound the relative error of w by 2^-56; else Gram + Cholesky "
-                       "(DESIGN.md s6.5)" + (
-                           "; column shards decide from the all-reduced shard sums (every rank "
-                           "alike) and exchange X u and each product E d" if world > 1 else "")}
-        # E-apply launches past a sweep's iteration count return at once: the roofline's
-        # bytes per launch are a pass's bytes x (passes run / launches), its time the average
-        # over all launches (what a rocprofv3 kernel trace averages)
-        ctx_pass_frac = (dp / brackets) if (dom == "eapply" and brackets) else 1.0
-        # the mixed plan's products stream the fp32 copy of X (4 B per element)
-        ctx_pass32 = ((mix1["products32"] - mix0["products32"]) / brackets
-                      if (dom == "eapply" and brackets) else 0.0)
+    if full:
+        dom_ms, _, _ = eng.kernel_times()
+        brackets = eng.timed_brackets()
+        # the exact kernel instances the timed sweeps launched (the PMC evidence is matched on
+        # them)
+        instances = {ph: bb.kernel_instance(ph) for ph in SINGLE_KERNEL_PHASES}
+        nid1 = eng.nid_stats()
+        mix1 = eng.nid_mixed()
+        eng.enable_timing(False)
+        nid = None
+        ctx_pass_frac = 1.0
+        ctx_pass32 = 0.0
+        if nid1["mode"] >= 0:
+            dc = nid1["cheb_sweeps"] - nid0["cheb_sweeps"]
+            dp = nid1["products"] - nid0["products"]
+            nid = {"timed_sweeps": args.steps, "chebyshev_sweeps": dc,
+                   "cholesky_sweeps": nid1["chol_sweeps"] - nid0["chol_sweeps"],
+                   "eapply_passes_per_chebyshev_sweep": (dp / dc) if dc else None,
+                   "mixed_plan_sweeps": mix1["mixed_sweeps"] - mix0["mixed_sweeps"],
+                   "fp32_passes_per_chebyshev_sweep": (
+                       (mix1["products32"] - mix0["products32"]) / dc if dc else None),
+                   "eps_last": nid1["eps"],
+                   "rule": "per sweep on the device: Chebyshev iteration on the certified "
+                           "spectrum interval [1, 1 + eps], eps >= lambda_max(X D X') / sig2 "
+                           "(the least of the trace and thresholded sums + T Lambda, Lambda >= "
+                           "lambda_max(X X') certified at setup), when K iterates (at most the "
+                           "cost model's cap) bound the relative error of w by 2^-56; else Gram "
+                           "+ Cholesky (DESIGN.md s6.5)" + (
+                               "; column shards decide from the all-reduced shard sums (every "
+                               "rank alike) and exchange X u and each product E d"
+                               if world > 1 else "")}
+            # E-apply launches past a sweep's iteration count return at once: the roofline's
+            # bytes per launch are a pass's bytes x (passes run / launches), its time the
+            # average over all launches (what a rocprofv3 kernel trace averages)
+            ctx_pass_frac = (dp / brackets) if (dom == "eapply" and brackets) else 1.0
+            # the mixed plan's products stream the fp32 copy of X (4 B per element)
+            ctx_pass32 = ((mix1["products32"] - mix0["products32"]) / brackets
+                          if (dom == "eapply" and brackets) else 0.0)
     flags = eng.error_flags()
     st = eng.state()
     if not (math.isfinite(st["tau"]) and math.isfinite(st["sig2"])) or flags:
         log(f"[rank {rank}] WARNING: state tau={st['tau']} sig2={st['sig2']} flags={flags}")
+    if args.dump_outputs:
+        # what the last timed sweep left, before any --full run below moves the chain on
+        outs = final_state(engines, dist)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
 
     gram_name = ("pair-list sparse Gram (fp64)" if sparse else
                  ("X'Omega X " if logit else "") +
                  ("ozaki-II int8 (fp64-accurate)" if eng.gram_mode() == bb.GRAM_OZAKI
                   else "fp64 mfma"))
-    ctx = dict(bb=bb, eng=eng, kind=kind, n=n, p=p, p_loc=p_loc, gram_mode=eng.gram_mode(),
-               gram_name=gram_name, pass_frac=ctx_pass_frac, pass32_frac=ctx_pass32,
-               window=(args.steps, args.warmup),
-               nid_cheb=nid_phase_cheb,
-               instances=instances)
-    fitted = None
-    if mode == "single" and not logit and not args.no_fitted:
-        fitted = fitted_regime(bb, eng, kind, n, p, alpha, t)
-        t += 10000
-    ref_proto = None
-    if mode == "single" and not args.no_fitted:
-        ref_proto = reference_protocol(runner, sync_all)
-    # the Gram's instances as launched (by the fitted-regime run when the timed sweeps formed none)
-    ctx_gram = dict(ctx, instances=dict(instances, **{
-        ph: instances.get(ph) or bb.kernel_instance(ph) for ph in ("gram", "reduce", "chol")}))
-    traffic_world = 1 if mode == "single" else world
-    roof = roofline_for(dom, dom_ms, ctx, traffic_world)
-    roof["timing"] = ("HIP events on rank 0's engine stream around "
-                      + ("every timed launch" if stride == 1 else
-                         f"the launch of every {stride}th timed sweep ({brackets} launches)"))
-    secondary = None
-    # the Gram's roofline beside the dominant kernel's: from this run's phase split when its
-    # sweeps formed the Gram, else from the fitted-regime run (near-identity sweeps skip it)
-    gram_src = (phases, f"HIP events at phase starts, {nph} untimed sweeps")
-    if nid_phase_cheb and fitted:
-        gram_src = (fitted["phases_ms"], "HIP events at phase starts, fitted-regime run")
-    if dom != "gram" and "gram" in gram_src[0] and not (nid_phase_cheb and not fitted):
-        secondary = roofline_for("gram", gram_src[0]["gram"], ctx_gram, traffic_world)
-        secondary["timing"] = gram_src[1]
-    gram_total_ms = sum(phases.get(k, 0.0) for k in ("ozprep", "gram", "reduce"))
+    more = {}  # the --full fields of the result line
+    if full:
+        ctx = dict(bb=bb, eng=eng, kind=kind, n=n, p=p, p_loc=p_loc, gram_mode=eng.gram_mode(),
+                   gram_name=gram_name, pass_frac=ctx_pass_frac, pass32_frac=ctx_pass32,
+                   window=(args.steps, args.warmup),
+                   nid_cheb=nid_phase_cheb,
+                   instances=instances)
+        fitted = None
+        if mode == "single" and not logit and not args.no_fitted:
+            fitted = fitted_regime(bb, eng, kind, n, p, alpha, t)
+            t += 10000
+        ref_proto = None
+        if mode == "single" and not args.no_fitted:
+            ref_proto = reference_protocol(runner, sync_all)
+        # the Gram's instances as launched (by the fitted-regime run when the timed sweeps
+        # formed none)
+        ctx_gram = dict(ctx, instances=dict(instances, **{
+            ph: instances.get(ph) or bb.kernel_instance(ph) for ph in ("gram", "reduce", "chol")}))
+        traffic_world = 1 if mode == "single" else world
+        roof = roofline_for(dom, dom_ms, ctx, traffic_world)
+        roof["timing"] = ("HIP events on rank 0's engine stream around "
+                          + ("every timed launch" if stride == 1 else
+                             f"the launch of every {stride}th timed sweep ({brackets} launches)"))
+        secondary = None
+        # the Gram's roofline beside the dominant kernel's: from this run's phase split when its
+        # sweeps formed the Gram, else from the fitted-regime run (near-identity sweeps skip it)
+        gram_src = (phases, f"HIP events at phase starts, {nph} untimed sweeps")
+        if nid_phase_cheb and fitted:
+            gram_src = (fitted["phases_ms"], "HIP events at phase starts, fitted-regime run")
+        if dom != "gram" and "gram" in gram_src[0] and not (nid_phase_cheb and not fitted):
+            secondary = roofline_for("gram", gram_src[0]["gram"], ctx_gram, traffic_world)
+            secondary["timing"] = gram_src[1]
+        gram_total_ms = sum(phases.get(k, 0.0) for k in ("ozprep", "gram", "reduce"))
 
-    cpu = cpu_more = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_sweeps > 0:
-        cpu, cpu_more = cpu_baselines(args, n, p, alpha, kind, cpu_sweeps)
+        cpu = cpu_more = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_sweeps > 0:
+            cpu, cpu_more = cpu_baselines(args, n, p, alpha, kind, cpu_sweeps)
+        more = {
+            "roofline": roof,
+            "roofline_secondary": secondary,
+            "phases_ms": {k: round(v, 4) for k, v in phases.items()},
+            "sweep_ms_phase_events": sweep_ms_phases,
+            "gram_total_ms": gram_total_ms,
+            "cpu_baseline": cpu,
+            "parity_check": parity,
+            "near_identity": nid,
+            "fitted_regime": fitted,
+            "reference_protocol": ref_proto,
+        }
+        if cpu_more:
+            more["cpu_baselines"] = cpu_more
 
     value = args.steps / elapsed
     if rank == 0:
@@ -887,20 +973,10 @@ def run_chain(args, n, p, alpha, kind, mode):
             "data": ("synthetic (SURVEY.md 8(d) design, seed 20240501"
                      + (f", Bernoulli({SPARSE_DENSITY}) sparsity)" if sparse else ")")),
             "config": config,
-            "roofline": roof,
-            "roofline_secondary": secondary,
-            "phases_ms": {k: round(v, 4) for k, v in phases.items()},
-            "sweep_ms_phase_events": sweep_ms_phases,
-            "gram_total_ms": gram_total_ms,
-            "cpu_baseline": cpu,
-            "parity_check": parity,
             "setup_s": setup_s,
-            "near_identity": nid,
-            "fitted_regime": fitted,
-            "reference_protocol": ref_proto,
+            "full": full,
         }
-        if cpu_more:
-            rec["cpu_baselines"] = cpu_more
+        rec.update(more)
         print(json.dumps(rec), flush=True)
     if grp:
         grp.close()
@@ -1137,8 +1213,12 @@ def small_chain(args, n, p, alpha):
     wall = time.perf_counter() - t_setup0
     runtime = float(out["runtime"])
     value = args.steps / runtime
+    if args.dump_outputs:
+        # the last recorded sweep of the traces the call returned
+        dump_outputs(args.dump_outputs,
+                     {k: out[k][-1] for k in ("beta", "lambda", "sig2", "tau", "alpha")})
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle
 
         ns = args.cpu_sweeps if args.cpu_sweeps is not None else 20000
@@ -1168,9 +1248,10 @@ def small_chain(args, n, p, alpha):
                    "alpha": alpha, "beta_step": "p x p Cholesky (reference-literal)",
                    "parallelism": "replicas only (p <= n)",
                    "kernel": "k_small_chain (whole sweeps in one workgroup)"},
-        "roofline": roof,
-        "cpu_baseline": cpu, "call_wall_s": wall,
+        "call_wall_s": wall, "full": args.full,
     }
+    if args.full:
+        rec.update(roofline=roof, cpu_baseline=cpu)
     print(json.dumps(rec), flush=True)
 
 

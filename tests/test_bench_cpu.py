@@ -53,6 +53,31 @@ def test_unsharded_workloads_refuse_multi_gpu(workload):
     assert "does not shard" in r.stderr
 
 
+def test_dump_outputs_writes_float64_within_its_budget(tmp_path):
+    """--dump-outputs: float64 .npy files; past the byte budget an array above its share is cut
+    to the same sorted sample of its entries every time, the small ones are kept whole."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    big = np.arange(5000, dtype=np.float32).reshape(50, 100)
+    arrays = {"big": big, "tau": 0.25, "sig2": np.float64(2.0)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["big"], big) and got["tau"].tolist() == [0.25]
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=3 * 8 * 1000)
+    b, c = (np.load(tmp_path / d / "big.npy") for d in ("b", "c"))
+    assert b.shape == (1000,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and set(b.tolist()) <= set(big.ravel().tolist())
+    assert np.load(tmp_path / "b" / "sig2.npy").tolist() == [2.0]
+    total = sum(f.stat().st_size for f in (tmp_path / "b").iterdir())
+    assert total <= 3 * 8 * 1000 + 3 * 128  # the budget and a header per file
+    assert bench.DUMP_BUDGET_BYTES < 64 * 10 ** 6
+
+
 def test_dominant_phase_roofline_formulas():
     """roofline_for: the Cholesky entry's flop rate and latency model follow DESIGN.md s8
     (m^3/3 flop per launch, m_pad/64 dependent block steps)."""

@@ -12,6 +12,6 @@ fi
 i=0
 for m in ${MODES:-20=1 20=0 20=1 20=0}; do
   i=$((i+1)); f=gpurun_out/ll_b${i}_${m//[=,]/_}
-  timeout -k 10 300 python -u bench.py --workload ${WL:-c4} --steps 300 --warmup 30 --no-cpu-baseline --no-fitted --tuning $m > $f.json 2> $f.err || exit 1
+  timeout -k 10 300 python -u bench.py --full --workload ${WL:-c4} --steps 300 --warmup 30 --no-cpu-baseline --no-fitted --tuning $m > $f.json 2> $f.err || exit 1
   python -c "import json;d=json.loads([l for l in open('$f.json') if l.startswith('{')][-1]);print('$m', round(d['value'],1), round(d['ms_per_step'],4), d['phases_ms'])"
 done

@@ -12,6 +12,6 @@ fi
 i=0
 for m in ${MODES:-18=1 18=0 18=1 18=0}; do
   i=$((i+1)); f=gpurun_out/px_b${i}_${m//[=,]/_}
-  BB_FORCE_RCCL=1 timeout -k 10 200 python -u bench.py --cols 6250 --steps 20 --warmup 5 --no-cpu-baseline --no-fitted --tuning 16=2 --tuning $m > $f.json 2> $f.err || exit 1
+  BB_FORCE_RCCL=1 timeout -k 10 200 python -u bench.py --full --cols 6250 --steps 20 --warmup 5 --no-cpu-baseline --no-fitted --tuning 16=2 --tuning $m > $f.json 2> $f.err || exit 1
   python -c "import json;d=json.loads([l for l in open('$f.json') if l.startswith('{')][-1]);print('$m', round(d['value'],1), round(d['ms_per_step'],4), d['phases_ms'])"
 done

@@ -2,7 +2,8 @@
 # One GPU session: the GPU tests (TESTS, default the whole -m gpu suite; PYTEST_ARGS extra
 # arguments, e.g. "-k shard"), then the bench lines listed in BENCHES (";"-separated argument
 # lists for bench.py; leading VAR=VALUE words are exported for that bench only, e.g.
-# "BB_FORCE_RCCL=1 --cols 6250 --no-fitted"), then the commands in EXTRA (";"-separated, run
+# "BB_FORCE_RCCL=1 --full --cols 6250 --no-fitted"; --full for the roofline, phase split and
+# CPU baselines beside the timed sweeps), then the commands in EXTRA (";"-separated, run
 # from the repo root).  Each step runs under its own time limit.  A fault, abort, segfault or
 # timeout ends the script; test failures (status 1) and expected refusals do not.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1

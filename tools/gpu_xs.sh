@@ -12,6 +12,6 @@ fi
 i=0
 for m in ${MODES:-7=3 7=2 7=3 7=2}; do
   i=$((i+1)); f=gpurun_out/xs_b${i}_${m//[=,]/_}
-  timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fitted --tuning $m > $f.json 2> $f.err || exit 1
+  timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fitted --tuning $m > $f.json 2> $f.err || exit 1
   python -c "import json;d=json.load(open('$f.json'));r=d['roofline'];print('$m', round(d['value'],1), r['kernel'], round(r['kernel_ms_avg']*1e3,1), d['phases_ms'])"
 done

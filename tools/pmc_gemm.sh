@@ -7,7 +7,7 @@ mkdir -p $OUT
 run() {  # $1 = name, rest = counters
     local name=$1; shift
     timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-include-regex "k_oz_gemm|k_oz_residues" \
-        -d $OUT/$name -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 \
+        -d $OUT/$name -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 \
         --gram ozaki --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; exit 1; }
     echo "$name ok"
 }

@@ -7,6 +7,6 @@ ROUND=${ROUND:-r02}
 OUT=gpurun_out/prof_$ROUND
 mkdir -p "$OUT"
 timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d "$OUT/l2" -o run --output-format csv \
-    -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/l2_bench.json" \
+    -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/l2_bench.json" \
     2> "$OUT/l2_bench.err" || { echo "L2 pass failed ($?)"; exit 1; }
 echo "L2 pass ok"

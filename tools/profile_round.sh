@@ -17,7 +17,7 @@ mkdir -p "$OUT"
 python3 -c "from bayesbridge_amd._build import source_sha; print(source_sha())" > "$OUT/source_sha.txt"
 # and the code identity of every kernel in the library it runs (bayesbridge_amd/_kernel_code.py)
 python3 -m bayesbridge_amd._kernel_code > "$OUT/kernel_code.json" || exit 1
-ARGS="--no-cpu-baseline $*"
+ARGS="--full --no-cpu-baseline $*"
 WIN="--steps ${STEPS:-20} --warmup ${WARMUP:-5}"
 set -o pipefail
 # PASS=kt|fetch|write runs that one pass (one GPU step per call); unset: all three in turn

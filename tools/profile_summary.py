@@ -69,7 +69,7 @@ def main():
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     steps = cfg.get("_steps", "")
     lines = [f"# rocprofv3 --kernel-trace --stats of: python3 bench.py {steps}"
-             f"--no-cpu-baseline ({wl or f'n={n}, p={p}'}, 1 GPU)",
+             f"--full --no-cpu-baseline ({wl or f'n={n}, p={p}'}, 1 GPU)",
              f"{'kernel':48s} {'calls':>6s} {'avg_us':>10s} {'min_us':>10s} {'tot_ms':>9s}  share"]
     avg_us = {}
     for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):

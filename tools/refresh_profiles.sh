@@ -8,9 +8,9 @@ mkdir -p gpurun_out
 R=${ROUND:-r03}
 for wl in ${WORKLOADS:-c3}; do
     case $wl in
-        c1) args="--workload c1 --steps 20000 --warmup 2000" ;;
-        c5) args="--workload c5 --steps 200 --warmup 20" ;;
-        *) args="--workload $wl --steps 1000 --warmup 100" ;;
+        c1) args="--full --workload c1 --steps 20000 --warmup 2000" ;;
+        c5) args="--full --workload c5 --steps 200 --warmup 20" ;;
+        *) args="--full --workload $wl --steps 1000 --warmup 100" ;;
     esac
     timeout -k 10 600 python -u bench.py $args > gpurun_out/bench_$wl.json 2> gpurun_out/bench_$wl.err \
         || { echo "bench $wl failed ($?)"; exit 1; }

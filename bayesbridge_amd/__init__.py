@@ -24,7 +24,8 @@ from . import _build
 
 __all__ = ["bridge_reg_stb", "bridge_reg", "retstable_ld", "set_seed", "get_rng_state",
            "set_rng_state", "Engine", "EngineConfig", "library", "device_count",
-           "sample_lambda", "retstable_batch", "gram", "chol_solve"]
+           "sample_lambda", "retstable_batch", "gram", "chol_solve", "bridge_reg_stb_chains",
+           "ChainBatch"]
 
 _lib: Optional[ctypes.CDLL] = None
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -67,7 +68,10 @@ EXPORTED_SYMBOLS = [
     "bb_pg_batch", "bb_group_create_rccl", "bb_group_sync", "bb_set_device_count",
     "bb_set_trace_budget", "bb_debug_interrupt_after", "bb_last_call_info",
     "bb_engine_set_timed_phase", "bb_engine_set_timing_stride", "bb_set_chol_version",
-    "bb_set_tuning",
+    "bb_set_tuning", "bridge_reg_stable_chains", "bb_chains_create", "bb_chains_destroy",
+    "bb_chains_count", "bb_chains_resident_per_cu", "bb_chains_init_state", "bb_chains_run",
+    "bb_chains_sync", "bb_chains_get_trace", "bb_chains_get_state", "bb_chains_set_state",
+    "bb_chains_error_flags",
 ]
 
 
@@ -153,6 +157,22 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_phase_name.restype = c.c_char_p
     L.retstable_LD.argtypes = [_dp, _dp, _dp, _dp, _ip]
     L.bridge_reg_stable.argtypes = [_dp] * 7 + [_dp] * 9 + [_ip] * 4 + [_dp, _ip]
+    L.bridge_reg_stable_chains.argtypes = [_dp] * 7 + [_dp] * 9 + [_ip] * 4 + [_dp, _ip, _ip]
+    L.bb_chains_create.argtypes = [c.POINTER(bb_config), c.c_int, _dp, _dp,
+                                   c.POINTER(c.c_void_p)]
+    L.bb_chains_destroy.argtypes = [c.c_void_p]
+    L.bb_chains_count.argtypes = [c.c_void_p]
+    L.bb_chains_resident_per_cu.argtypes = [c.c_void_p]
+    L.bb_chains_init_state.argtypes = [c.c_void_p]
+    L.bb_chains_run.argtypes = [c.c_void_p, c.c_uint64, c.c_int, c.c_int, c.c_int, c.c_int]
+    L.bb_chains_sync.argtypes = [c.c_void_p]
+    L.bb_chains_get_trace.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int, _dp, _dp, _dp, _dp,
+                                      _dp]
+    L.bb_chains_get_state.argtypes = [c.c_void_p, c.c_int, _dp, _dp, _dp, _dp, _dp]
+    L.bb_chains_set_state.argtypes = [c.c_void_p, c.c_int, _dp, c.c_double, c.c_double,
+                                      c.c_double]
+    L.bb_chains_error_flags.argtypes = [c.c_void_p, c.c_int]
+    L.bb_chains_error_flags.restype = c.c_uint
     L.bridge_reg_stable_csc.argtypes = ([_dp] * 6 + [_ip, _ip, _dp] + [_dp] * 9 + [_ip] * 4 +
                                         [_dp, _ip])
     L.bb_engine_create_csc.argtypes = [c.POINTER(bb_config), _ip, _ip, _dp, _dp,
@@ -403,6 +423,51 @@ def bridge_reg_stb(y, X, nsamp, alpha=0.5, sig2_shape=0.0, sig2_scale=0.0, nu_sh
                             *hyper)
     out = {"beta": beta.T.copy(), "lambda": lam.T.copy(), "sig2": sig2, "tau": tau,
            "alpha": alph, "runtime": rt.value}
+    if colnames is not None:
+        out["colnames"] = list(colnames)
+    return out
+
+
+def bridge_reg_stb_chains(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0, sig2_scale=0.0,
+                          nu_shape=2.0, nu_rate=2.0, alpha_a=1.0, alpha_b=1.0, sig2_true=0.0,
+                          tau_true=0.0, burn=500, ortho=False, colnames=None):
+    """``nchains`` independent chains of bridge.reg.stb in one call, through
+    ``.C("bridge_reg_stable_chains", ...)``: chain c is exactly what the c-th of ``nchains``
+    consecutive ``bridge_reg_stb`` calls would return.  Small dense designs (P <= 32, P <= N or
+    ortho, alpha known) run every chain side by side in one launch per block of sweeps.
+
+    Returns a dict: beta (K x M x P), lambda (K x M x P), sig2, tau, alpha (K x M), runtime
+    (one number for the batch).
+    """
+    L = library()
+    _require_gpu()
+    y = np.asarray(y, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    R, P = X.shape
+    N = y.shape[0]
+    M, K = int(nsamp), int(nchains)
+    if not check_parameters(N, R, M, sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                            alpha_b) or not _is_above(K, 1, "nchains"):
+        raise ValueError("bridge_reg_stb_chains: invalid parameters")
+    # P x M x K column-major is (K, M, P) in C order
+    beta = np.zeros((K, M, P))
+    lam = np.zeros((K, M, P))
+    sig2 = np.zeros((K, M))
+    tau = np.zeros((K, M))
+    alph = np.zeros((K, M))
+    d = lambda v: ctypes.byref(ctypes.c_double(float(v)))  # noqa: E731
+    i = lambda v: ctypes.byref(ctypes.c_int(int(v)))  # noqa: E731
+    rt = ctypes.c_double(0.0)
+    Xf = np.asfortranarray(X)
+    L.bridge_reg_stable_chains(_p(beta), _p(lam), _p(sig2), _p(tau), _p(alph), _p(y), _p(Xf),
+                               d(sig2_shape), d(sig2_scale), d(nu_shape), d(nu_rate),
+                               d(alpha_a), d(alpha_b), d(sig2_true), d(tau_true), d(alpha),
+                               i(P), i(N), i(M), i(burn), ctypes.byref(rt),
+                               i(1 if ortho else 0), i(K))
+    out = {"beta": beta, "lambda": lam, "sig2": sig2, "tau": tau, "alpha": alph,
+           "runtime": rt.value}
     if colnames is not None:
         out["colnames"] = list(colnames)
     return out
@@ -1133,6 +1198,83 @@ class Engine:
     def close(self):
         if getattr(self, "_h", None):
             library().bb_engine_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ChainBatch:
+    """``nchains`` independent chains of one small dense design resident on one GPU, advanced
+    together by one launch per run (bb_chains_*).  Chain c draws under the key
+    (cfg.seed, cfg.stream + c); cfg.trace_capacity is each chain's ring capacity."""
+
+    def __init__(self, cfg: EngineConfig, nchains: int, X, y):
+        L = library()
+        _require_gpu()
+        self.cfg = cfg
+        self._c = cfg.to_c()
+        self.p = self._c.p
+        X = np.asfortranarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        assert X.shape == (cfg.n, cfg.p), X.shape
+        h = ctypes.c_void_p()
+        _check(L.bb_chains_create(ctypes.byref(self._c), int(nchains), _p(X), _p(y),
+                                  ctypes.byref(h)), "bb_chains_create")
+        self._h = h
+        self.nchains = int(L.bb_chains_count(h))
+
+    def resident_per_cu(self) -> int:
+        """Workgroups (chains) the runtime keeps resident on one compute unit."""
+        return int(library().bb_chains_resident_per_cu(self._h))
+
+    def init_state(self):
+        _check(library().bb_chains_init_state(self._h), "bb_chains_init_state")
+
+    def run(self, t0: int, count: int, first_slot: int = -1, slot_step: int = 1,
+            mcmc_phase: int = 1):
+        _check(library().bb_chains_run(self._h, int(t0), int(count), int(first_slot),
+                                       int(slot_step), int(mcmc_phase)), "bb_chains_run")
+
+    def sync(self):
+        _check(library().bb_chains_sync(self._h), "bb_chains_sync")
+
+    def trace(self, chain: int, slot0: int, count: int):
+        p = self.p
+        beta = np.zeros((p, count), order="F")
+        lam = np.zeros((p, count), order="F")
+        sig2, tau, alpha = np.zeros(count), np.zeros(count), np.zeros(count)
+        _check(library().bb_chains_get_trace(self._h, int(chain), slot0, count, _p(beta),
+                                             _p(lam), _p(sig2), _p(tau), _p(alpha)),
+               "bb_chains_get_trace")
+        return dict(beta=beta, **{"lambda": lam}, sig2=sig2, tau=tau, alpha=alpha)
+
+    def state(self, chain: int):
+        beta, lam = np.zeros(self.p), np.zeros(self.p)
+        tau, sig2, alpha = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        _check(library().bb_chains_get_state(self._h, int(chain), _p(beta), _p(lam),
+                                             ctypes.byref(tau), ctypes.byref(sig2),
+                                             ctypes.byref(alpha)), "bb_chains_get_state")
+        return dict(beta=beta, **{"lambda": lam}, tau=tau.value, sig2=sig2.value,
+                    alpha=alpha.value)
+
+    def set_state(self, chain: int, beta, tau, sig2, alpha):
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        _check(library().bb_chains_set_state(self._h, int(chain), _p(beta), tau, sig2, alpha),
+               "bb_chains_set_state")
+
+    def error_flags(self, chain: int) -> int:
+        f = int(library().bb_chains_error_flags(self._h, int(chain)))
+        if f == 0xFFFFFFFF and _err():  # the message is empty after a successful read
+            raise RuntimeError(f"bb_chains_error_flags failed: {_err()}")
+        return f
+
+    def close(self):
+        if getattr(self, "_h", None):
+            library().bb_chains_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -106,8 +107,9 @@ struct RRng {
     }
 } g_rrng;
 
-// Key for one .C call: from R's RNG if present, else (seed, stream++).
-void next_call_key(uint64_t *k0, uint64_t *k1) {
+// Key for one .C call: from R's RNG if present, else (seed, stream++).  A call that runs
+// `count` chains takes the streams k1 .. k1 + count - 1 (one seed drawn under R's RNG).
+void next_call_key(uint64_t *k0, uint64_t *k1, int count = 1) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_use_r_rng && g_rrng.ok()) {
         g_rrng.get();
@@ -120,7 +122,8 @@ void next_call_key(uint64_t *k0, uint64_t *k1) {
         return;
     }
     *k0 = g_seed;
-    *k1 = g_stream++;
+    *k1 = g_stream;
+    g_stream += (uint64_t)count;
 }
 
 // ---------------------------------------------------------------------------
@@ -299,6 +302,10 @@ int g_nid_poll = 1;
 // (1, the default); 2: unsharded, the launch's last stream workgroup reduces and decides too;
 // 0: k_nid_sums + k_nid_reduce after the launch
 int g_nid_fold = 1;
+// bb_set_tuning key 21: chain batches of at least 2 x CUs chains created from now on run the
+// 256-thread instance, two chains per CU (faster in aggregate there; its chains
+// match the oracle but are not bit for bit those of sequential calls)
+int g_chains_packed = 0;
 static const char *kPhaseNames[PH_COUNT] = {"pre", "scalars", "lambda", "pg", "ozprep", "gram",
                                             "xu", "reduce", "form", "chol", "solve", "beta",
                                             "xb", "alpha", "nid", "eapply", "end"};
@@ -1613,7 +1620,143 @@ void ring_copy(double *dst, const double *src, size_t count) {
     HIPCHECK(hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost));
 }
 
+// Enqueue throttle of the .C drivers: mark() records the work enqueued so far on a stream and
+// waits until at most two marked blocks are ahead of the device.
+struct Throttle {
+    hipEvent_t evring[3] = {nullptr, nullptr, nullptr};
+    long nmarks = 0;
+    ~Throttle() {
+        for (auto e : evring)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(hipStream_t stream) {
+        hipEvent_t &e = evring[nmarks % 3];
+        if (!e) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHECK(hipEventRecord(e, stream));
+        if (nmarks >= 2) HIPCHECK(hipEventSynchronize(evring[(nmarks - 2) % 3]));
+        ++nmarks;
+    }
+};
+
+// Why a configuration cannot run as a chain batch (nullptr: it can): the batch kernel is the
+// fused small chain, so the conditions are those of bb_engine::fused for the stable mixture.
+const char *chains_refusal(const bb_config &c) {
+    if (c.n <= 0 || c.p <= 0) return "n and p must be positive";
+    if (c.world > 1) return "a chain batch runs on one device (world == 1)";
+    if (c.p_local > 0 && c.p_local != c.p) return "a chain batch holds every column (p_local == p)";
+    if (c.method != 0 && c.method != 1)
+        return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or 1)";
+    if (c.p > kSmallChainMaxP) return "a chain batch needs p <= 32";
+    if (c.p > c.n && !c.ortho) return "a chain batch needs p <= n (or the orthogonal design)";
+    if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
+    return nullptr;
+}
+
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// Chain batch: K chains of one small design, a workgroup each (bb_small.hip k_small_chains).
+// One engine (`proto`, never run) holds what the chains share -- X, y, X'X, X'y and the
+// least-squares start -- and draws each chain's pre-burn tau under that chain's key; the
+// state, the error word and the trace rings are per chain ([chain][p], [chain][slot][p]).
+// ---------------------------------------------------------------------------
+struct bb_chains {
+    bb_engine *proto = nullptr;
+    int K = 0, p = 0, cap = 1;
+    std::vector<void *> owned;
+    double *beta = nullptr, *lam = nullptr;
+    DevScalars *sc = nullptr, *sc0 = nullptr;  // sc0: the scalars every chain starts from
+    uint32_t *err = nullptr;
+    double *tr_beta = nullptr, *tr_lam = nullptr, *tr_sig2 = nullptr, *tr_tau = nullptr,
+           *tr_alpha = nullptr;
+    Throttle ahead;
+
+    ~bb_chains() {
+        if (proto && proto->stream) (void)hipStreamSynchronize(proto->stream);
+        for (void *q : owned) (void)hipFree(q);
+        delete proto;
+    }
+    hipStream_t stream() const { return proto->stream; }
+    void check_chain(int c) const {
+        if (c < 0 || c >= K) throw HipError("chain index out of range");
+    }
+
+    void init_state() {
+        bb_engine *e = proto;
+        hipStream_t s = e->stream;
+        const size_t pb = (size_t)p * sizeof(double);
+        e->cfg.stream = base_stream;
+        engine_init_state_local(e);  // least-squares start, starting scalars, X beta
+        HIPCHECK(hipMemcpyAsync(sc0, e->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
+        HIPCHECK(hipMemsetAsync(lam, 0, (size_t)K * pb, s));
+        const bool draw_tau = e->method != 3 && !e->hy.know_tau;
+        for (int c = 0; c < K; ++c) {
+            const size_t ring = (size_t)c * cap;
+            if (draw_tau) {  // BridgeWrapper.cpp:262 under the chain's own key
+                HIPCHECK(hipMemcpyAsync(e->sc, sc0, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
+                e->clear_err();
+                e->cfg.stream = base_stream + (uint64_t)c;
+                e->pre_and_scalars(0, 0, 1);
+            }
+            HIPCHECK(hipMemcpyAsync(beta + (size_t)c * p, e->beta, pb, hipMemcpyDeviceToDevice, s));
+            HIPCHECK(hipMemcpyAsync(sc + c, e->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
+            HIPCHECK(hipMemcpyAsync(err + c, e->err, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            // trace slot 0: the starting values, as a single engine leaves them
+            HIPCHECK(hipMemcpyAsync(tr_beta + ring * p, e->beta, pb, hipMemcpyDeviceToDevice, s));
+            HIPCHECK(hipMemcpyAsync(tr_tau + ring, e->tr_tau, sizeof(double),
+                                    hipMemcpyDeviceToDevice, s));
+            HIPCHECK(hipMemcpyAsync(tr_sig2 + ring, e->tr_sig2, sizeof(double),
+                                    hipMemcpyDeviceToDevice, s));
+            HIPCHECK(hipMemcpyAsync(tr_alpha + ring, e->tr_alpha, sizeof(double),
+                                    hipMemcpyDeviceToDevice, s));
+        }
+        e->cfg.stream = base_stream;
+        e->clear_err();
+        HIPCHECK(hipStreamSynchronize(s));
+    }
+
+    void run(uint64_t t0, int count, int first_slot, int slot_step) {
+        bb_engine *e = proto;
+        launch_small_chains(e->stream, K, e->X, e->n_pad, e->n, e->p, e->y, e->G, e->p_pad,
+                            e->cvec, e->gdiag, e->method == 3, beta, lam, sc, e->hy, e->cfg.seed,
+                            base_stream, t0, count, first_slot, slot_step, cap, tr_beta, tr_lam,
+                            tr_sig2, tr_tau, tr_alpha, err, packed);
+    }
+
+    void throttle() { ahead.mark(stream()); }
+
+    // Trace slots [slot0, slot0 + count) of EVERY chain -> samples [s0, s0 + count) of the
+    // P x M x K (M x K) outputs: one strided copy per contiguous run of the ring and trace.
+    void copy_out(int slot0, int count, int s0, int m, double *obeta, double *olam, double *osig2,
+                  double *otau, double *oalpha) {
+        auto strided = [&](double *dst, const double *src, size_t w, int k, int sl, int run) {
+            if (!dst) return;
+            if (K == 1 || (run == cap && run == m)) {  // one contiguous block (no ring wrap)
+                ring_copy(dst + (size_t)(s0 + k) * w, src + (size_t)sl * w,
+                          (size_t)K * run * w);
+                return;
+            }
+            HIPCHECK(hipMemcpy2D(dst + (size_t)(s0 + k) * w, (size_t)m * w * sizeof(double),
+                                 src + (size_t)sl * w, (size_t)cap * w * sizeof(double),
+                                 (size_t)run * w * sizeof(double), (size_t)K,
+                                 hipMemcpyDeviceToHost));
+        };
+        for (int k = 0; k < count;) {
+            const int sl = (slot0 + k) % cap;
+            const int run = std::min(count - k, cap - sl);
+            strided(obeta, tr_beta, (size_t)p, k, sl, run);
+            strided(olam, tr_lam, (size_t)p, k, sl, run);
+            strided(osig2, tr_sig2, 1, k, sl, run);
+            strided(otau, tr_tau, 1, k, sl, run);
+            strided(oalpha, tr_alpha, 1, k, sl, run);
+            k += run;
+        }
+    }
+
+    uint64_t base_stream = 0;
+    // the 256-thread instance (two chains per CU): bb_set_tuning key 21 and K >= 2 CUs
+    int packed = 0;
+};
 
 // ---------------------------------------------------------------------------
 // C ABI
@@ -2125,6 +2268,186 @@ int bb_engine_error_flags(bb_engine *e, uint32_t *flags) {
         return -1;
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Chain batch (struct bb_chains above)
+// ---------------------------------------------------------------------------
+int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const double *y,
+                     bb_chains **out) {
+    *out = nullptr;
+    if (nchains < 1) {
+        set_error("bb_chains_create: nchains must be at least 1 (got %d)", nchains);
+        return -1;
+    }
+    if (const char *why = chains_refusal(*cfg)) {
+        set_error("bb_chains_create: %s", why);
+        return -1;
+    }
+    bb_chains *b = new bb_chains();
+    try {
+        bb_config c = *cfg;
+        b->K = nchains;
+        b->p = c.p;
+        b->cap = c.trace_capacity < 1 ? 1 : c.trace_capacity;
+        b->base_stream = c.stream;
+        c.p_local = c.p;
+        c.trace_capacity = 1;  // the shared engine records its own slot 0 only
+        if (bb_engine_create(&c, X, y, &b->proto) != 0) throw HipError(g_last_error);
+        if (!b->proto->fused || b->proto->method == 4)
+            throw HipError("this design does not run as a fused small chain");
+        int cus = 0;
+        HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
+        b->packed = g_chains_packed && nchains >= 2 * cus;
+        auto &o = b->owned;
+        const size_t K = (size_t)nchains, p = (size_t)c.p, cap = (size_t)b->cap;
+        b->beta = dalloc<double>(K * p, o);
+        b->lam = dalloc<double>(K * p, o);
+        b->sc = dalloc<DevScalars>(K, o);
+        b->sc0 = dalloc<DevScalars>(1, o);
+        b->err = dalloc<uint32_t>(K, o);
+        b->tr_beta = dalloc<double>(K * cap * p, o);
+        b->tr_lam = dalloc<double>(K * cap * p, o);
+        b->tr_sig2 = dalloc<double>(K * cap, o);
+        b->tr_tau = dalloc<double>(K * cap, o);
+        b->tr_alpha = dalloc<double>(K * cap, o);
+    } catch (std::exception &ex) {
+        const std::string msg = ex.what();
+        delete b;
+        set_error("bb_chains_create: %s", msg.c_str());
+        return -1;
+    }
+    *out = b;
+    return 0;
+}
+
+void bb_chains_destroy(bb_chains *b) { delete b; }
+int bb_chains_count(const bb_chains *b) { return b->K; }
+
+int bb_chains_resident_per_cu(const bb_chains *b) {
+    if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
+    return small_chains_resident_per_cu(b->proto->n, b->p, b->packed);
+}
+
+int bb_chains_init_state(bb_chains *b) {
+    try {
+        HIPCHECK(hipSetDevice(b->proto->cfg.device));
+        b->init_state();
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_run(bb_chains *b, uint64_t t0, int count, int first_slot, int slot_step,
+                  int mcmc_phase) {
+    (void)mcmc_phase;  // selects the prior of the alpha MH step: alpha is known here
+    try {
+        HIPCHECK(hipSetDevice(b->proto->cfg.device));
+        b->run(t0, count, first_slot, slot_step);
+        HIPCHECK(hipGetLastError());
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_sync(bb_chains *b) {
+    try {
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_get_trace(bb_chains *b, int chain, int slot0, int count, double *beta,
+                        double *lambda, double *sig2, double *tau, double *alpha) {
+    try {
+        b->check_chain(chain);
+        if (slot0 < 0 || count < 0) throw HipError("bb_chains_get_trace: slot0 and count must be >= 0");
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        const size_t pl = (size_t)b->p, ring = (size_t)chain * b->cap;
+        for (int k = 0; k < count;) {
+            const int s = (slot0 + k) % b->cap;
+            const int run = std::min(count - k, b->cap - s);
+            if (beta) ring_copy(beta + k * pl, b->tr_beta + (ring + s) * pl, run * pl);
+            if (lambda) ring_copy(lambda + k * pl, b->tr_lam + (ring + s) * pl, run * pl);
+            if (sig2) ring_copy(sig2 + k, b->tr_sig2 + ring + s, run);
+            if (tau) ring_copy(tau + k, b->tr_tau + ring + s, run);
+            if (alpha) ring_copy(alpha + k, b->tr_alpha + ring + s, run);
+            k += run;
+        }
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_get_state(bb_chains *b, int chain, double *beta, double *lambda, double *tau,
+                        double *sig2, double *alpha) {
+    try {
+        b->check_chain(chain);
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        const size_t pl = (size_t)b->p;
+        if (beta)
+            HIPCHECK(hipMemcpy(beta, b->beta + chain * pl, pl * sizeof(double),
+                               hipMemcpyDeviceToHost));
+        if (lambda)
+            HIPCHECK(hipMemcpy(lambda, b->lam + chain * pl, pl * sizeof(double),
+                               hipMemcpyDeviceToHost));
+        DevScalars s;
+        HIPCHECK(hipMemcpy(&s, b->sc + chain, sizeof(s), hipMemcpyDeviceToHost));
+        if (tau) *tau = s.tau;
+        if (sig2) *sig2 = s.sig2;
+        if (alpha) *alpha = s.alpha;
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau, double sig2,
+                        double alpha) {
+    try {
+        b->check_chain(chain);
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        const size_t pl = (size_t)b->p;
+        HIPCHECK(hipMemcpy(b->beta + chain * pl, beta, pl * sizeof(double),
+                           hipMemcpyHostToDevice));
+        DevScalars s;
+        HIPCHECK(hipMemcpy(&s, b->sc + chain, sizeof(s), hipMemcpyDeviceToHost));
+        s.tau = tau;
+        s.sig2 = sig2;
+        s.alpha = alpha;
+        HIPCHECK(hipMemcpy(b->sc + chain, &s, sizeof(s), hipMemcpyHostToDevice));
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+// ~0u when the flags cannot be read; bb_last_error then says why and is empty otherwise, which
+// tells a failure from a flag word with every bit set
+unsigned bb_chains_error_flags(bb_chains *b, int chain) {
+    g_last_error.clear();
+    try {
+        b->check_chain(chain);
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpyAsync(&f, b->err + chain, sizeof(f), hipMemcpyDeviceToHost,
+                                b->stream()));
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        return f;
+    } catch (std::exception &ex) {
+        set_error("bb_chains_error_flags: %s", ex.what());
+        return ~0u;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -3335,7 +3658,7 @@ bb_config stable_call_config(const double *sig2_shape, const double *sig2_scale,
                              const double *nu_shape, const double *nu_rate, const double *alpha_a,
                              const double *alpha_b, const double *true_sig2,
                              const double *true_tau, const double *true_alpha, int p, int n,
-                             int m, const int *ortho) {
+                             int m, const int *ortho, int nchains = 1) {
     bb_config c;
     bb_config_default(&c);
     c.n = n;
@@ -3353,7 +3676,7 @@ bb_config stable_call_config(const double *sig2_shape, const double *sig2_scale,
     c.ortho = *ortho != 0;
     c.trace_capacity = m < 1 ? 1 : m;
     c.device = g_device;
-    next_call_key(&c.seed, &c.stream);
+    next_call_key(&c.seed, &c.stream, nchains);
     return c;
 }
 
@@ -3383,12 +3706,9 @@ struct Chain {
     std::vector<int> j0s;
     bb_group *grp = nullptr;
     int p = 0, cap = 1;
-    hipEvent_t evring[3] = {nullptr, nullptr, nullptr};
-    long nmarks = 0;
+    Throttle ahead;
 
     ~Chain() {
-        for (auto e : evring)
-            if (e) (void)hipEventDestroy(e);
         if (grp) bb_group_destroy(grp);
         for (auto *e : eng) bb_engine_destroy(e);
     }
@@ -3412,11 +3732,7 @@ struct Chain {
     // the exchanges) and waits until at most two marked blocks are ahead of the device.
     void throttle() {
         HIPCHECK(hipSetDevice(eng[0]->cfg.device));
-        hipEvent_t &e = evring[nmarks % 3];
-        if (!e) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPCHECK(hipEventRecord(e, eng[0]->stream));
-        if (nmarks >= 2) HIPCHECK(hipEventSynchronize(evring[(nmarks - 2) % 3]));
-        ++nmarks;
+        ahead.mark(eng[0]->stream);
     }
     // trace slots [slot0, slot0 + count) -> samples [s0, s0 + count) of the P x M outputs
     int copy_out(int slot0, int count, int s0, double *beta, double *lam, double *sig2,
@@ -3487,16 +3803,16 @@ int chain_build(Chain &ch, bb_config c, int ntr, Create create) {
 
 enum Outcome { OUT_OK = 0, OUT_ERROR = 1, OUT_INTERRUPTED = 2 };
 
-// Burn-in then the MCMC samples, in blocks of 10 sweeps between interrupt polls (at most two
-// blocks queued ahead of the device), the trace ring copied out whenever it is full.
-// Sample s >= 1 runs at t = t_base + s; burn-in is `nburn` sweeps in slot 0 from t = 1.
-Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, double *betap,
-                    double *lambdap, double *sig2p, double *taup, double *alphap,
-                    double *runtime, double *up = nullptr, double *shapep = nullptr) {
-    // BridgeWrapper.cpp:273-275, 295-297 poll every 10 sweeps.  A fused engine runs a
-    // whole block in one launch at ~15-30 us per sweep, so it polls every 50 (< 2 ms) and
-    // pays the launch and LDS-staging prologue once per 50 sweeps instead of per 10.
-    const int kBlock = ch.fused() ? 50 : 10;
+// The schedule of every .C sampler call: burn-in then the MCMC samples, in blocks of kBlock
+// sweeps between interrupt polls (at most two blocks queued ahead of the device), the trace
+// ring copied out whenever it is full.  Sample s >= 1 runs at t = t_base + s; burn-in is
+// `nburn` sweeps in slot 0 from t = 1.  `ch` is what is driven -- a Chain, or a chain batch
+// (ChainsRun) -- with init / run / sync / throttle returning 0 or throwing, and `cap` ring
+// slots; copy_out(slot0, count, s0) moves ring slots to samples [s0, s0 + count) of the
+// caller's outputs, report_flags() prints the numerical failures after a complete run.
+template <class C, class CopyOut, class Report>
+Outcome drive_schedule(C &ch, int kBlock, int nburn, uint64_t t_base, int m, int b,
+                       double *runtime, CopyOut copy_out, Report report_flags) {
     *runtime = 0.0;
     if (ch.init() != 0) return OUT_ERROR;
     bool interrupted = false;
@@ -3526,29 +3842,43 @@ Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, double 
                 next = s + cnt;
             }
             if (ch.sync() != 0) return OUT_ERROR;
-            if (ch.copy_out(copied % ch.cap, next - copied, copied, betap, lambdap, sig2p, taup,
-                            alphap, up, shapep) != 0)
-                return OUT_ERROR;
+            if (copy_out(copied % ch.cap, next - copied, copied) != 0) return OUT_ERROR;
             copied = next;
         }
-        if (interrupted && copied == 0 && ch.sync() == 0)
-            (void)ch.copy_out(0, 1, 0, betap, lambdap, sig2p, taup, alphap, up, shapep);
+        if (interrupted && copied == 0 && ch.sync() == 0) (void)copy_out(0, 1, 0);
         *runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
         if (interrupted) {
             printf("Interrupted: %i of %i samples returned.\n", std::max(copied, 1), m);
             return OUT_INTERRUPTED;
         }
-        const uint32_t f = ch.flags();
-        if (f & ~4u) {
-            printf("Error: numerical failure in the device sampler (flags %u)\n", f);
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-        }
+        report_flags();
     } catch (std::exception &ex) {
         set_error("%s", ex.what());
         return OUT_ERROR;
     }
     return OUT_OK;
+}
+
+Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, double *betap,
+                    double *lambdap, double *sig2p, double *taup, double *alphap,
+                    double *runtime, double *up = nullptr, double *shapep = nullptr) {
+    // BridgeWrapper.cpp:273-275, 295-297 poll every 10 sweeps.  A fused engine runs a
+    // whole block in one launch at ~15-30 us per sweep, so it polls every 50 (< 2 ms) and
+    // pays the launch and LDS-staging prologue once per 50 sweeps instead of per 10.
+    const int kBlock = ch.fused() ? 50 : 10;
+    return drive_schedule(
+        ch, kBlock, nburn, t_base, m, b, runtime,
+        [&](int slot0, int count, int s0) {
+            return ch.copy_out(slot0, count, s0, betap, lambdap, sig2p, taup, alphap, up, shapep);
+        },
+        [&] {
+            const uint32_t f = ch.flags();
+            if (f & ~4u) {
+                printf("Error: numerical failure in the device sampler (flags %u)\n", f);
+                printf("Aborting Gibbs sampler.\n");
+                fflush(stdout);
+            }
+        });
 }
 
 void print_banner(const char *title, const bb_config &c, int b, int m) {
@@ -3605,6 +3935,94 @@ Outcome stable_dense(const bb_config &c, const double *yp, const double *Xp, int
             return bb_engine_create(cc, Xp + (size_t)j0 * n, yp, e);
         },
         b, betap, lambdap, sig2p, taup, alphap, runtime, title);
+}
+
+// A chain batch as drive_schedule drives it: every run advances all K chains.
+struct ChainsRun {
+    bb_chains *b;
+    int cap;
+    int init() { return bb_chains_init_state(b); }
+    int run(uint64_t t0, int count, int slot, int step, int mcmc) {
+        return bb_chains_run(b, t0, count, slot, step, mcmc);
+    }
+    int sync() { return bb_chains_sync(b); }
+    void throttle() { b->throttle(); }
+};
+
+// K chains of a small design as one batch on drive_chain's schedule (50-sweep blocks, as a
+// fused single chain).  The trace budget bounds the batch: each chain's ring gets a K-th.
+Outcome stable_chains_batch(const bb_config &c0, int K, const double *yp, const double *Xp, int b,
+                            double *betap, double *lambdap, double *sig2p, double *taup,
+                            double *alphap, double *runtime) {
+    const int m = c0.trace_capacity;
+    *runtime = 0.0;
+    bb_config c = c0;
+    {
+        const size_t per = (size_t)2 * c.p * sizeof(double) + 3 * sizeof(double);
+        size_t cap = g_trace_budget / (size_t)K / per;
+        if (cap < 16) cap = 16;
+        c.trace_capacity = (int)std::min<size_t>(cap, (size_t)(m < 1 ? 1 : m));
+    }
+    bb_chains *raw = nullptr;
+    if (bb_chains_create(&c, K, Xp, yp, &raw) != 0) return OUT_ERROR;
+    std::unique_ptr<bb_chains> ch(raw);
+    g_last_devices = 1;
+    g_last_capacity = ch->cap;
+    ChainsRun run{raw, ch->cap};
+    return drive_schedule(
+        run, 50, b + 1, (uint64_t)b + 1, m, b, runtime,
+        [&](int slot0, int count, int s0) {
+            ch->copy_out(slot0, count, s0, m, betap, lambdap, sig2p, taup, alphap);
+            return 0;
+        },
+        [&] {
+            std::vector<uint32_t> f(K, 0u);
+            HIPCHECK(hipMemcpy(f.data(), ch->err, (size_t)K * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost));
+            for (int k = 0; k < K; ++k)
+                if (f[k] & ~4u) {
+                    printf("Error: numerical failure in the device sampler (flags %u) in chain "
+                           "%i\n", f[k], k);
+                    printf("Aborting Gibbs sampler.\n");
+                    fflush(stdout);
+                }
+        });
+}
+
+// bridge_reg_stable_chains: the batch where the fused small chain applies, else the K chains
+// one after another through the single-chain driver on streams k1 + c.
+Outcome stable_chains(const bb_config &c, int K, const double *yp, const double *Xp, int b,
+                      double *betap, double *lambdap, double *sig2p, double *taup,
+                      double *alphap, double *runtime) {
+    const char *title = "Bridge Regression (mix. of normals):";
+    const size_t m = (size_t)c.trace_capacity, pm = (size_t)c.p * m;
+    *runtime = 0.0;
+    if (chains_refusal(c) == nullptr) {
+        print_banner(title, c, b, (int)m);
+        g_last_interrupted = 0;
+        const Outcome o = stable_chains_batch(c, K, yp, Xp, b, betap, lambdap, sig2p, taup,
+                                              alphap, runtime);
+        if (o == OUT_ERROR) {
+            printf("Error: %s\n", g_last_error.c_str());
+            printf("Aborting Gibbs sampler.\n");
+            fflush(stdout);
+        }
+        if (g_verbose && o == OUT_OK)
+            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime,
+                   (int)m, K);
+        g_last_interrupted = o == OUT_INTERRUPTED;
+        return o;
+    }
+    for (int k = 0; k < K; ++k) {
+        bb_config ck = c;
+        ck.stream = c.stream + (uint64_t)k;
+        double rt = 0.0;
+        const Outcome o = stable_dense(ck, yp, Xp, b, betap + k * pm, lambdap + k * pm,
+                                       sig2p + k * m, taup + k * m, alphap + k * m, &rt, title);
+        *runtime += rt;
+        if (o == OUT_INTERRUPTED) return o;
+    }
+    return OUT_OK;
 }
 
 }  // namespace
@@ -3755,6 +4173,11 @@ int bb_set_tuning(int key, int value) {
             if (value >= 0) g_nid_fold = value > 2 ? 2 : value;
             return old;
         }
+        case 21: {
+            const int old = g_chains_packed;
+            if (value >= 0) g_chains_packed = value ? 1 : 0;
+            return old;
+        }
         case 15: {
             const int old = g_lam_lend;
             if (value >= 0) g_lam_lend = value ? 1 : 0;
@@ -3786,6 +4209,29 @@ void bridge_reg_stable(double *betap, double *lambdap, double *sig2p, double *ta
                                            ortho);
     if (stable_dense(c, yp, Xp, *burn, betap, lambdap, sig2p, taup, alphap, runtime,
                      "Bridge Regression (mix. of normals):") == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
+void bridge_reg_stable_chains(double *betap, double *lambdap, double *sig2p, double *taup,
+                              double *alphap, const double *yp, const double *Xp,
+                              const double *sig2_shape, const double *sig2_scale,
+                              const double *nu_shape, const double *nu_rate,
+                              const double *alpha_a, const double *alpha_b,
+                              const double *true_sig2, const double *true_tau,
+                              const double *true_alpha, const int *P, const int *N,
+                              const int *M, const int *burn, double *runtime,
+                              const int *ortho, const int *nchains) {
+    if (*nchains < 1) {  // before a key is taken or an output is touched
+        set_error("bridge_reg_stable_chains: nchains must be at least 1 (got %d)", *nchains);
+        printf("Error: %s\n", g_last_error.c_str());
+        fflush(stdout);
+        return;
+    }
+    const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                           alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                           ortho, *nchains);
+    if (stable_chains(c, *nchains, yp, Xp, *burn, betap, lambdap, sig2p, taup, alphap,
+                      runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 

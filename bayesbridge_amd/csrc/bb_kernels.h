@@ -390,6 +390,21 @@ void launch_small_chain(hipStream_t s, const double *X, int ldx, int n, int p, c
                         int slot_step, int cap, double *tr_beta, double *tr_lam, double *tr_sig2,
                         double *tr_tau, double *tr_alpha, uint32_t *err);
 
+// The same sweeps for `nchains` independent chains in one launch, a workgroup per chain
+// (k_small_chains): chain c has beta + c p, lam + c p, sc[c], err[c], the trace rings
+// tr_beta + c cap p (tr_sig2 + c cap, ...) and the key (k0, k1 + c); X, y, G, cvec and gdiag are
+// shared.  small_chains_resident_per_cu: the workgroups the runtime keeps resident on one CU
+// for an n x p design (-1 if the query fails).  packed: the 256-thread instance, two
+// workgroups per CU (another summation order of rss and S_alpha than the 512-thread one).
+void launch_small_chains(hipStream_t s, int nchains, const double *X, int ldx, int n, int p,
+                         const double *y, const double *G, int ldg, const double *cvec,
+                         const double *gdiag, int ortho, double *beta, double *lam, DevScalars *sc,
+                         Hyper hy, uint64_t k0, uint64_t k1, uint64_t t0, int count,
+                         int first_slot, int slot_step, int cap, double *tr_beta, double *tr_lam,
+                         double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err,
+                         int packed);
+int small_chains_resident_per_cu(int n, int p, int packed);
+
 // Whole triangle-mixture sweeps (non-orthogonal design, alpha known, p <= kTriChainMaxP) in
 // one single-workgroup launch (bb_tri.hip k_tri_chain): S_alpha / rss, tau and sig2, then
 // omega, u and the rtnorm_gibbs passes of launch_tri_update in one wave, `count` sweeps from

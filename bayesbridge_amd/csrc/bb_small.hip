@@ -67,14 +67,18 @@ void small_phase_ticks(unsigned long long out[4]) {
 // L lanes per coefficient in the lambda draw (stable_spec_draw<L, I>), the p x p system
 // dynamic LDS holds
 // X (n x p, column-major) when it fits, else X is read from HBM each sweep.
-template <int NT, int L, int I>
-__global__ __launch_bounds__(NT) void k_small_chain(
+// small_chain_body is the whole sweep loop of one chain in one workgroup: k_small_chain runs
+// it once, k_small_chains once per workgroup on that chain's state, so the arithmetic exists
+// once.
+// LOST: a chain whose state is no longer finite skips its lambda draws (k_small_chains).
+template <int NT, int L, int I, bool LOST>
+__device__ __forceinline__ void small_chain_body(
     const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
     const double *__restrict__ G, int ldg, const double *__restrict__ cvec,
     const double *__restrict__ gdiag, int ortho, int x_lds, double *beta, double *lam,
-    DevScalars *sc, Hyper hy, Key key, uint64_t t0, int count, int first_slot, int slot_step,
-    int cap, double *tr_beta, double *tr_lam, double *tr_sig2, double *tr_tau, double *tr_alpha,
-    uint32_t *err) {
+    DevScalars *sc, Hyper hy, Key key, uint64_t t0, int count, int first_slot,
+    int slot_step, int cap, double *tr_beta, double *tr_lam, double *tr_sig2, double *tr_tau,
+    double *tr_alpha, uint32_t *err) {
     extern __shared__ double sX[];
     __shared__ double sU[kSmallMaxP][kSmallMaxP + 1];  // U, row-major (U[k][j])
     __shared__ double sG[kSmallMaxP][kSmallMaxP + 1];
@@ -111,12 +115,15 @@ __global__ __launch_bounds__(NT) void k_small_chain(
     __syncthreads();
     const double tau_shape = hy.nu_shape + ((double)p) / alpha;
     const double sig2_shape = hy.sig2_shape + 0.5 * (double)n;
-    // upper-triangle entries owned by this thread: e = tid and tid + NT, e = j (j + 1) / 2 + i
-    bool own[2];
-    int oi[2], oj[2];
-    double av[2] = {0.0, 0.0};
+    // upper-triangle entries owned by this thread: e = tid, tid + NT, ..., e = j (j + 1) / 2 + i
+    // (two per thread at NT = 512, three at NT = 256)
+    constexpr int H = (kSmallMaxP * (kSmallMaxP + 1) / 2 + NT - 1) / NT;
+    bool own[H];
+    int oi[H], oj[H];
+    double av[H];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < H; ++h) {
+        av[h] = 0.0;
         const int e = tid + h * NT;
         own[h] = !ortho && e < p * (p + 1) / 2;
         int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
@@ -188,8 +195,18 @@ __global__ __launch_bounds__(NT) void k_small_chain(
             const int j = jb + tid / L;
             const bool act = j < p;
             const double b = act ? sb[j] : 0.0;
-            const double x = stable_spec_draw<L, I>(act, b * b / (tau * tau), 0.5 * alpha, 1.0,
-                                                    key, t, (uint64_t)j, err);
+            // A NaN tilt (the chain's state is no longer finite) fails every test of the
+            // rejection sampler, which then gives up after BB_MAX_STABLE_ROUNDS rounds --
+            // seconds per sweep -- with error bit 2 and a NaN draw.  A batch takes that outcome
+            // at once (LOST): a lost chain must not hold a CU that other chains wait for.
+            const double h = b * b / (tau * tau);
+            const bool lost = LOST && act && h != h;
+            double x = stable_spec_draw<L, I>(act && !lost, h, 0.5 * alpha, 1.0, key, t,
+                                              (uint64_t)j, err);
+            if (lost) {
+                x = __builtin_nan("");
+                if ((tid % L) == 0) atomicOr(err, 2u);
+            }
             if (act && (tid % L) == 0) {
                 sl[j] = 2 * x;
                 if (slot >= 0) tr_lam[(size_t)slot * p + j] = 2 * x;
@@ -218,14 +235,14 @@ __global__ __launch_bounds__(NT) void k_small_chain(
             // the chain.)
             const double dl = tau * tau;
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
+            for (int h = 0; h < H; ++h)
                 if (own[h]) {
                     const int i = oi[h], j = oj[h];
                     av[h] = sG[i][j] + (i == j ? sl[i] * sig2 / dl : 0.0);
                 }
             for (int kk = 0; kk < p; ++kk) {
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
+                for (int h = 0; h < H; ++h)
                     if (own[h] && oi[h] == kk && oj[h] == kk) {
                         if (!(av[h] > 0.0)) atomicOr(err, 8u);
                         av[h] = sqrt(av[h]);
@@ -234,14 +251,14 @@ __global__ __launch_bounds__(NT) void k_small_chain(
                 __syncthreads();
                 const double d = sU[kk][kk];
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
+                for (int h = 0; h < H; ++h)
                     if (own[h] && oi[h] == kk && oj[h] > kk) {
                         av[h] = av[h] / d;
                         sU[kk][oj[h]] = av[h];
                     }
                 __syncthreads();
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
+                for (int h = 0; h < H; ++h)
                     if (own[h] && oi[h] > kk) av[h] -= sU[kk][oi[h]] * sU[kk][oj[h]];
             }
             if (wid == 0) {
@@ -284,6 +301,42 @@ __global__ __launch_bounds__(NT) void k_small_chain(
     }
 }
 
+template <int NT, int L, int I>
+__global__ __launch_bounds__(NT) void k_small_chain(
+    const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
+    const double *__restrict__ G, int ldg, const double *__restrict__ cvec,
+    const double *__restrict__ gdiag, int ortho, int x_lds, double *beta, double *lam,
+    DevScalars *sc, Hyper hy, Key key, uint64_t t0, int count, int first_slot, int slot_step,
+    int cap, double *tr_beta, double *tr_lam, double *tr_sig2, double *tr_tau, double *tr_alpha,
+    uint32_t *err) {
+    small_chain_body<NT, L, I, false>(X, ldx, n, p, y, G, ldg, cvec, gdiag, ortho, x_lds, beta, lam, sc,
+                               hy, key, t0, count, first_slot, slot_step, cap, tr_beta, tr_lam,
+                               tr_sig2, tr_tau, tr_alpha, err);
+}
+
+// K independent chains, one workgroup each (blockIdx.x = chain c): the design, G, c and the
+// hyper-parameters are shared and read-only; the state (beta, lam: stride p; sc, err: one per
+// chain), the trace rings ([chain][slot][p], [chain][slot]) and the Philox key
+// (key.k0, key.k1 + c) are the chain's own.  No workgroup waits for another, so K may exceed
+// what the device holds at once: later workgroups start as earlier ones end.
+// (two waves per SIMD: at most 256 VGPRs, so that two 256-thread workgroups share a CU)
+template <int NT, int L, int I>
+__global__ __launch_bounds__(NT, 2) void k_small_chains(
+    const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
+    const double *__restrict__ G, int ldg, const double *__restrict__ cvec,
+    const double *__restrict__ gdiag, int ortho, int x_lds, double *beta, double *lam,
+    DevScalars *sc, Hyper hy, Key key, uint64_t t0, int count, int first_slot, int slot_step,
+    int cap, double *tr_beta, double *tr_lam, double *tr_sig2, double *tr_tau, double *tr_alpha,
+    uint32_t *err) {
+    const size_t c = blockIdx.x;
+    const Key ck{key.k0, key.k1 + (uint64_t)c};
+    const size_t ring = c * (size_t)cap;
+    small_chain_body<NT, L, I, true>(X, ldx, n, p, y, G, ldg, cvec, gdiag, ortho, x_lds, beta + c * p,
+                               lam + c * p, sc + c, hy, ck, t0, count, first_slot, slot_step, cap,
+                               tr_beta + ring * p, tr_lam + ring * p, tr_sig2 + ring,
+                               tr_tau + ring, tr_alpha + ring, err + c);
+}
+
 // Dynamic LDS above the 64 KB default needs a per-kernel opt-in: done once for every
 // instance (thread-safe static init), with the launch error checked by the caller.
 template <int NT, int L, int I>
@@ -317,6 +370,73 @@ void launch_small_chain(hipStream_t s, const double *X, int ldx, int n, int p, c
     if (p <= 8) go(k_small_chain<512, 64, 16>, 512);
     else if (p <= 16) go(k_small_chain<512, 32, 8>, 512);
     else go(k_small_chain<512, 16, 8>, 512);
+}
+
+namespace {
+
+using SmallChainsKernel = void (*)(const double *, int, int, int, const double *, const double *,
+                                   int, const double *, const double *, int, int, double *,
+                                   double *, DevScalars *, Hyper, Key, uint64_t, int, int, int,
+                                   int, double *, double *, double *, double *, double *,
+                                   uint32_t *);
+
+// the batch instance for p coefficients (the lanes per coefficient of launch_small_chain), its
+// LDS opt-in made once
+SmallChainsKernel small_chains_instance(int p, int packed, int *nt) {
+    static const SmallChainsKernel inst[5] = {k_small_chains<512, 64, 16>,
+                                              k_small_chains<512, 32, 8>,
+                                              k_small_chains<512, 16, 8>,
+                                              k_small_chains<256, 32, 8>,
+                                              k_small_chains<256, 16, 8>};
+    static const bool optin = [] {
+        for (SmallChainsKernel k : inst)
+            (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      kSmallXLds);
+        return true;
+    }();
+    (void)optin;
+    static_assert(kSmallMaxP == 32, "instances above cover p <= 32");
+    *nt = packed ? 256 : 512;
+    if (packed) return inst[p <= 8 ? 3 : 4];  // p > 16: the lambda draws in two passes
+    return inst[p <= 8 ? 0 : p <= 16 ? 1 : 2];
+}
+
+// dynamic LDS of a launch: X when it fits, and no more than X needs -- a CU holds as many
+// chains as its 160 KB allow
+size_t small_chain_shm(int n, int p, int *x_lds) {
+    const size_t xbytes = (size_t)n * p * sizeof(double);
+    *x_lds = xbytes <= kSmallXLds;
+    return *x_lds ? xbytes : 0;
+}
+
+}  // namespace
+
+void launch_small_chains(hipStream_t s, int nchains, const double *X, int ldx, int n, int p,
+                         const double *y, const double *G, int ldg, const double *cvec,
+                         const double *gdiag, int ortho, double *beta, double *lam, DevScalars *sc,
+                         Hyper hy, uint64_t k0, uint64_t k1, uint64_t t0, int count,
+                         int first_slot, int slot_step, int cap, double *tr_beta, double *tr_lam,
+                         double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err,
+                         int packed) {
+    if (count <= 0 || nchains <= 0) return;
+    int x_lds = 0, nt = 0;
+    const size_t shm = small_chain_shm(n, p, &x_lds);
+    const SmallChainsKernel kern = small_chains_instance(p, packed, &nt);
+    kern<<<nchains, nt, shm, s>>>(
+        X, ldx, n, p, y, G, ldg, cvec, gdiag, ortho, x_lds, beta, lam, sc, hy, Key{k0, k1}, t0,
+        count, first_slot, slot_step, cap, tr_beta, tr_lam, tr_sig2, tr_tau, tr_alpha, err);
+}
+
+int small_chains_resident_per_cu(int n, int p, int packed) {
+    int x_lds = 0, blocks = 0, nt = 0;
+    const size_t shm = small_chain_shm(n, p, &x_lds);
+    const SmallChainsKernel kern = small_chains_instance(p, packed, &nt);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)kern, nt, shm) !=
+        hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return blocks;
 }
 
 }  // namespace bb

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["effective_size", "sum_stat"]
+__all__ = ["effective_size", "sum_stat", "rhat", "sum_stat_chains"]
 
 
 def _acov(x: np.ndarray, maxlag: int) -> np.ndarray:
@@ -84,3 +84,42 @@ def sum_stat(beta, runtime: float):
             "ess_summary": (float(ess.min()), float(np.median(ess)), float(ess.max())),
             "esr_summary": (float(esr.min()), float(np.median(esr)), float(esr.max())),
             "runtime": runtime}
+
+
+def rhat(x) -> np.ndarray:
+    """Split potential scale reduction factor of K chains: x is (K, M) or (K, M, P) and the
+    result a scalar array or (P,).  Each chain is split in halves (the middle draw dropped
+    when M is odd), giving 2K sequences of length n; with W the mean within-sequence variance
+    and B / n the variance of the sequence means, R-hat = sqrt(((n - 1) / n W + B / n) / W)
+    (Gelman et al., Bayesian Data Analysis 3rd ed., s11.4)."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim not in (2, 3):
+        raise ValueError("rhat: x must be (chains, draws) or (chains, draws, parameters)")
+    n = x.shape[1] // 2
+    if n < 2:
+        raise ValueError("rhat: at least four draws per chain are needed")
+    seq = np.concatenate([x[:, :n], x[:, x.shape[1] - n:]], axis=0)  # (2K, n[, P])
+    W = seq.var(axis=1, ddof=1).mean(axis=0)
+    B_over_n = seq.mean(axis=1).var(axis=0, ddof=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt((n - 1) / n + B_over_n / W)
+
+
+def sum_stat_chains(beta, runtime: float):
+    """sum_stat for K chains: beta is (K, M, P) (a (K, M) trace is one coefficient).  Per
+    coefficient: the pooled posterior mean and sd, the ESS summed over the chains (each
+    chain's coda effective size), ESS per second of the batch's runtime, and split R-hat."""
+    beta = np.asarray(beta, dtype=np.float64)
+    if beta.ndim == 2:
+        beta = beta[:, :, None]
+    K, M, P = beta.shape
+    ess = np.zeros(P)
+    for c in range(K):
+        ess += effective_size(beta[c])
+    esr = ess / runtime if runtime > 0 else np.full_like(ess, np.inf)
+    pooled = beta.reshape(K * M, P)
+    return {"mean": pooled.mean(axis=0), "sd": pooled.std(axis=0, ddof=1), "ess": ess,
+            "esr": esr, "rhat": rhat(beta),
+            "ess_summary": (float(ess.min()), float(np.median(ess)), float(ess.max())),
+            "esr_summary": (float(esr.min()), float(np.median(esr)), float(esr.max())),
+            "runtime": runtime, "chains": K}

@@ -263,6 +263,68 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
                         double alpha);
 
 /*
+ * Chain batch: `nchains` independent chains of one small dense design in ONE launch per run,
+ * a workgroup per chain (bb_small.hip k_small_chains).  Chain c draws under the key
+ * (cfg->seed, cfg->stream + c) and is, bit for bit, the chain a bb_engine with that key
+ * runs.  Creation succeeds exactly where a single engine runs its sweeps fused: the stable
+ * mixture with the p x p Cholesky or the orthogonal-design draw (method 0 / 1 with p <= n,
+ * or ortho), p <= 32, world == 1, alpha known (true_alpha > 0); otherwise -1 and
+ * bb_last_error says why.  The design upload, X'X, X'y and the least-squares start are done
+ * once for the batch.  cfg->trace_capacity is the ring capacity of EACH chain.  nchains may
+ * exceed what the device holds at once: later chains start as earlier ones finish.
+ * (With bb_set_tuning key 21 set, a batch of at least 2 x compute units chains runs the
+ * two-per-CU instance, which is not bit for bit the single engine's chain; see there.)
+ *
+ * init_state, run, sync, get_trace, get_state and set_state mean for chain `chain` what the
+ * bb_engine_* calls mean for a single engine; bb_chains_run advances every chain by `count`
+ * sweeps.  bb_chains_error_flags returns chain `chain`'s flag word (a failed Cholesky pivot
+ * sets bit 8 in its own chain's word only), or ~0u with a non-empty bb_last_error if the
+ * word cannot be read (bb_last_error is empty after a successful read).
+ * bb_chains_resident_per_cu reports how many of the batch's workgroups the runtime keeps
+ * resident on one compute unit (hipOccupancyMaxActiveBlocksPerMultiprocessor; -1 if the
+ * query fails).
+ */
+typedef struct bb_chains bb_chains;
+int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const double *y,
+                     bb_chains **out);
+void bb_chains_destroy(bb_chains *b);
+int bb_chains_count(const bb_chains *b);
+int bb_chains_resident_per_cu(const bb_chains *b);
+int bb_chains_init_state(bb_chains *b);
+int bb_chains_run(bb_chains *b, uint64_t t0, int count, int first_slot, int slot_step,
+                  int mcmc_phase);
+int bb_chains_sync(bb_chains *b);
+int bb_chains_get_trace(bb_chains *b, int chain, int slot0, int count, double *beta,
+                        double *lambda, double *sig2, double *tau, double *alpha);
+int bb_chains_get_state(bb_chains *b, int chain, double *beta, double *lambda, double *tau,
+                        double *sig2, double *alpha);
+int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau, double sig2,
+                        double alpha);
+unsigned bb_chains_error_flags(bb_chains *b, int chain);
+
+/*
+ * K independent chains of bridge_reg_stable in one call: the arguments of bridge_reg_stable
+ * with `nchains` appended.  The outputs gain a trailing chain dimension: betap and lambdap
+ * are P x M x K column-major, sig2p, taup and alphap are M x K; runtime is one number for the
+ * batch.  Chain c returns exactly what the c-th of K consecutive bridge_reg_stable calls
+ * would return: one call key is taken and chain c draws under (k0, k1 + c) (outside R the
+ * stream counter advances by K; under R's RNG one seed is drawn).  Small designs (where a
+ * single chain runs fused, see bb_chains_create) run as one chain batch, with the trace
+ * budget (bb_set_trace_budget) bounding the rings of the whole batch; every other design
+ * bridge_reg_stable accepts runs its K chains one after another.  nchains < 1 prints an
+ * error and returns without writing.
+ */
+void bridge_reg_stable_chains(double *betap, double *lambdap, double *sig2p, double *taup,
+                              double *alphap, const double *yp, const double *Xp,
+                              const double *sig2_shape, const double *sig2_scale,
+                              const double *nu_shape, const double *nu_rate,
+                              const double *alpha_a, const double *alpha_b,
+                              const double *true_sig2, const double *true_tau,
+                              const double *true_alpha, const int *P, const int *N,
+                              const int *M, const int *burn, double *runtime,
+                              const int *ortho, const int *nchains);
+
+/*
  * Shard group: `count` engines with cfg.rank = 0..count-1 and cfg.world = count, each
  * holding a column shard of one p > n chain.  Two kinds share the type:
  *   - bb_group_create: every member on ONE device, driven by one host thread, the per-sweep
@@ -379,7 +441,13 @@ void bb_set_trace_budget(long long bytes);
  * 12 significant bits, so the sums' order does not reach it);
  * key 20: the persistent backward solve hands each solved block to the next as 64-bit words
  * tagged with the solve's epoch, polled directly (1, the default), or behind a flag (0); the
- * same bits.
+ * same bits;
+ * key 21: chain batches (bb_chains_create, bridge_reg_stable_chains) of at least 2 x the
+ * device's compute units run a 256-thread instance of the batch kernel, two chains per
+ * compute unit (1), or the 512-thread instance at every size (0, the default).  The narrow
+ * instance is about 1.4 x faster in aggregate there and sums rss and S_alpha in another
+ * order: its chains match the CPU oracle within the whole-chain tolerances but are not bit
+ * for bit those of sequential bridge_reg_stable calls, hence opt-in.
  * A negative value changes nothing.  Returns the previous value, or -1 for an unknown key. */
 int bb_set_tuning(int key, int value);
 /* Test hook: the k-th interrupt poll from now reports an interrupt (k >= 0; -1 clears). */

@@ -1,0 +1,214 @@
+"""Aggregate rate of K independent small-design chains in one launch (bridge_reg_stb_chains,
+bb_small.hip k_small_chains) against one chain at a time.
+
+Designs: C1 (bench.py's n=100, p=20 synthetic design) and a diabetes-shaped 442 x 10 synthetic
+design.  For K in {1, 8, 64, CUs, 2 CUs, 4 CUs}: burn-in 500, 5000 samples, the post-burn
+runtime the call reports (it includes copying the traces out), aggregate sweeps/s = K nsamp /
+runtime, per-chain sweeps/s, and the resident workgroups per CU the runtime reports.  The
+kernel-only rate (ChainBatch.run without traces) separates the sweeps from the copy-out.
+K = 2 CUs and 4 CUs are measured a second time with bb_set_tuning key 21 (the 256-thread
+instance, two chains per CU) into the record's "chains_two_per_cu".
+
+Protocol: one warm-up call, then REPS rounds, each round visiting every K (and the
+single-chain bridge_reg_stb call) once, so slow drifts of the device hit every K alike; the
+median over rounds is reported with the min and max beside it.
+
+  python tools/bench_chains.py                 # both designs -> profiles/chains_{c1,db}.json
+  python tools/bench_chains.py --mode single --tree DIR   # bridge_reg_stb alone, from the
+                                                          # checkout at DIR (A/B with a parent)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED = 0xB4E5B41D6E
+CPU_CORE_C1 = 60323.0  # compiled reference-literal chain, one core (profiles/r06_bench_c1.json)
+
+
+def designs():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    out = {"c1": (bench.make_columns(100, 0, 20), bench.make_problem_y(100, 20)[0])}
+    rng = np.random.default_rng(20240501)
+    X = rng.standard_normal((442, 10))
+    X -= X.mean(axis=0)
+    b = np.r_[3.0, -2.0, 1.5, -1.0, 2.5, np.zeros(5)]
+    y = X @ b + 2.0 * rng.standard_normal(442)
+    out["db"] = (np.asfortranarray(X), y - y.mean())
+    return out
+
+
+def spread(v):
+    v = sorted(v)
+    return {"median": float(np.median(v)), "min": float(v[0]), "max": float(v[-1])}
+
+
+def kernel_rate(bb, X, y, K, nsamp):
+    """Sweeps/s of the batch kernel alone: blocks of 50 sweeps, no traces, one sync."""
+    n, p = X.shape
+    b = bb.ChainBatch(bb.EngineConfig(n=n, p=p, trace_capacity=1, seed=SEED), K, X, y)
+    try:
+        b.init_state()
+        b.run(1, 500, 0, 0, 0)
+        b.sync()
+        t0 = time.perf_counter()
+        for s in range(0, nsamp, 50):
+            b.run(501 + s, 50, -1, 1, 1)
+        b.sync()
+        dt = time.perf_counter() - t0
+        return K * nsamp / dt, b.resident_per_cu()
+    finally:
+        b.close()
+
+
+def single_kernel_rate(bb, X, y, nsamp):
+    """kernel_rate for one bb.Engine (k_small_chain): the batch kernel's K = 1 counterpart."""
+    n, p = X.shape
+    e = bb.Engine(bb.EngineConfig(n=n, p=p, trace_capacity=1, seed=SEED), X, y)
+    try:
+        e.init_state()
+        e.run(1, 500, 0, 0, 0)
+        e.sync()
+        t0 = time.perf_counter()
+        for s in range(0, nsamp, 50):
+            e.run(501 + s, 50, -1, 1, 1)
+        e.sync()
+        return nsamp / (time.perf_counter() - t0)
+    finally:
+        e.close()
+
+
+def bench_design(bb, name, X, y, cus, args, Ks=None):
+    Ks = Ks or [k for k in dict.fromkeys([1, 8, 64, cus, 2 * cus, 4 * cus])
+                if k <= args.max_chains]
+    nsamp, burn = args.nsamp, args.burn
+    bb.set_seed(SEED)
+    bb.bridge_reg_stb_chains(y, X, nsamp=200, nchains=2, burn=100)  # warm-up
+    bb.bridge_reg_stb(y, X, nsamp=200, burn=100)
+    rt = {K: [] for K in Ks}
+    wall = {K: [] for K in Ks}
+    kern = {K: [] for K in Ks}
+    single, single_kern = [], []
+    res = None
+    for _ in range(args.reps):
+        bb.set_seed(SEED)
+        single.append(nsamp / bb.bridge_reg_stb(y, X, nsamp=nsamp, burn=burn)["runtime"])
+        single_kern.append(single_kernel_rate(bb, X, y, nsamp))
+        for K in Ks:
+            bb.set_seed(SEED)
+            t0 = time.perf_counter()
+            out = bb.bridge_reg_stb_chains(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            wall[K].append(time.perf_counter() - t0)
+            rt[K].append(out["runtime"])
+            del out
+            kr, res = kernel_rate(bb, X, y, K, nsamp)
+            kern[K].append(kr)
+    rows = []
+    for K in Ks:
+        agg = [K * nsamp / r for r in rt[K]]
+        rows.append({"chains": K, "runtime_s": spread(rt[K]), "wall_s": spread(wall[K]),
+                     "aggregate_sweeps_per_s": spread(agg),
+                     "per_chain_sweeps_per_s": spread([a / K for a in agg]),
+                     "kernel_aggregate_sweeps_per_s": spread(kern[K]),
+                     "resident_per_cu": res})
+    one = rows[0]["aggregate_sweeps_per_s"]["median"]
+    for r in rows:
+        r["aggregate_vs_one_chain"] = r["aggregate_sweeps_per_s"]["median"] / one
+        r["kernel_vs_one_chain"] = (r["kernel_aggregate_sweeps_per_s"]["median"] /
+                                    rows[0]["kernel_aggregate_sweeps_per_s"]["median"])
+    rec = {"design": name, "n": int(X.shape[0]), "p": int(X.shape[1]), "nsamp": nsamp,
+           "burn": burn, "reps": args.reps, "compute_units": cus,
+           "single_call_sweeps_per_s": spread(single),
+           "single_kernel_sweeps_per_s": spread(single_kern), "chains": rows}
+    if name == "c1":
+        best = max(r["aggregate_sweeps_per_s"]["median"] for r in rows)
+        rec["cpu_core_sweeps_per_s"] = CPU_CORE_C1
+        rec["cpu_cores_worth"] = best / CPU_CORE_C1
+    return rec
+
+
+def bench_single(bb, args):
+    """bridge_reg_stb alone at both designs (one JSON line): the A/B against another checkout."""
+    out = {}
+    for name, (X, y) in designs().items():
+        bb.set_seed(SEED)
+        bb.bridge_reg_stb(y, X, nsamp=200, burn=100)
+        v = []
+        for _ in range(args.reps):
+            bb.set_seed(SEED)
+            v.append(args.nsamp / bb.bridge_reg_stb(y, X, nsamp=args.nsamp,
+                                                    burn=args.burn)["runtime"])
+        out[name] = spread(v)
+    print(json.dumps({"tree": args.tree, "single_call_sweeps_per_s": out}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--mode", choices=["chains", "single"], default="chains")
+    ap.add_argument("--tree", default=ROOT, help="checkout whose bayesbridge_amd is measured")
+    ap.add_argument("--designs", default="c1,db")
+    ap.add_argument("--nsamp", type=int, default=5000)
+    ap.add_argument("--burn", type=int, default=500)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--max-chains", type=int, default=1 << 20)
+    ap.add_argument("--tuning", default="",
+                    help="KEY=VALUE,...: bb_set_tuning before measuring (A/B of a variant build)")
+    ap.add_argument("--tag", default="", help="suffix of the output files' names")
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.tree))
+    import torch
+
+    import bayesbridge_amd as bb
+
+    bb.set_verbose(0)
+    for kv in filter(None, args.tuning.split(",")):
+        k, v = kv.split("=")
+        bb.set_tuning(int(k), int(v))
+    if args.mode == "single":
+        return bench_single(bb, args)
+    cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    for name, (X, y) in designs().items():
+        if name not in args.designs.split(","):
+            continue
+        rec = bench_design(bb, name, X, y, cus, args)
+        # the two-chains-per-CU instance (bb_set_tuning key 21) where it applies: K >= 2 CUs
+        big = [k for k in (2 * cus, 4 * cus) if k <= args.max_chains]
+        if big and not args.tuning and bb.set_tuning(21, -1) >= 0:
+            bb.set_tuning(21, 1)
+            try:
+                rec["chains_two_per_cu"] = bench_design(bb, name, X, y, cus, args, big)["chains"]
+            finally:
+                bb.set_tuning(21, 0)
+        rec["source_sha"] = bb._build.source_sha()
+        path = os.path.join(args.out_dir, f"chains_{name}{args.tag}.json")
+        with open(path, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        for r in rec["chains"]:
+            print(f"{name} K={r['chains']:5d} runtime {r['runtime_s']['median']:.4f} s  "
+                  f"aggregate {r['aggregate_sweeps_per_s']['median']:.0f} sweeps/s "
+                  f"[{r['aggregate_sweeps_per_s']['min']:.0f}, "
+                  f"{r['aggregate_sweeps_per_s']['max']:.0f}]  "
+                  f"kernel {r['kernel_aggregate_sweeps_per_s']['median']:.0f}  "
+                  f"x{r['aggregate_vs_one_chain']:.1f}  resident/CU {r['resident_per_cu']}",
+                  flush=True)
+        for r in rec.get("chains_two_per_cu", []):
+            print(f"{name} two per CU K={r['chains']:5d} aggregate "
+                  f"{r['aggregate_sweeps_per_s']['median']:.0f} sweeps/s "
+                  f"[{r['aggregate_sweeps_per_s']['min']:.0f}, "
+                  f"{r['aggregate_sweeps_per_s']['max']:.0f}]  kernel "
+                  f"{r['kernel_aggregate_sweeps_per_s']['median']:.0f}  "
+                  f"resident/CU {r['resident_per_cu']}", flush=True)
+        print(f"{name} single call {rec['single_call_sweeps_per_s']} kernel "
+              f"{rec['single_kernel_sweeps_per_s']}", flush=True)
+
+
+if __name__ == "__main__":
+    main()

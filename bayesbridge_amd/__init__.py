@@ -25,7 +25,7 @@ from . import _build
 __all__ = ["bridge_reg_stb", "bridge_reg", "retstable_ld", "set_seed", "get_rng_state",
            "set_rng_state", "Engine", "EngineConfig", "library", "device_count",
            "sample_lambda", "retstable_batch", "gram", "chol_solve", "bridge_reg_stb_chains",
-           "ChainBatch"]
+           "bridge_reg_tri_chains", "ChainBatch", "compute_units"]
 
 _lib: Optional[ctypes.CDLL] = None
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -71,7 +71,9 @@ EXPORTED_SYMBOLS = [
     "bb_set_tuning", "bridge_reg_stable_chains", "bb_chains_create", "bb_chains_destroy",
     "bb_chains_count", "bb_chains_resident_per_cu", "bb_chains_init_state", "bb_chains_run",
     "bb_chains_sync", "bb_chains_get_trace", "bb_chains_get_state", "bb_chains_set_state",
-    "bb_chains_error_flags",
+    "bb_chains_error_flags", "bridge_regression_chains", "bb_chains_get_tri_trace",
+    "bb_chains_set_tri_state", "bb_chains_get_tri_basis", "bb_chains_threads",
+    "bb_chains_set_threads", "bb_compute_units",
 ]
 
 
@@ -196,6 +198,14 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_rrtgamma_batch.argtypes = [c.c_int, _dp, _dp, _dp, _dp, c.c_uint64, c.c_uint64]
     L.bb_trunc_batch.argtypes = [c.c_int, c.c_int, _dp, _dp, _dp, _dp, _dp, c.c_uint64,
                                  c.c_uint64]
+    L.bridge_regression_chains.argtypes = ([_dp] * 9 + [_dp] * 9 + [_ip] * 4 + [_dp] +
+                                           [_ip] * 4)
+    L.bb_chains_get_tri_trace.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int, _dp, _dp]
+    L.bb_chains_set_tri_state.argtypes = [c.c_void_p, c.c_int, _dp]
+    L.bb_chains_get_tri_basis.argtypes = [c.c_void_p, _dp, _dp, _dp]
+    L.bb_chains_threads.argtypes = [c.c_void_p]
+    L.bb_compute_units.argtypes = [c.c_int]
+    L.bb_chains_set_threads.argtypes = [c.c_void_p, c.c_int]
     L.bb_engine_get_tri_trace.argtypes = [c.c_void_p, c.c_int, c.c_int, _dp, _dp]
     L.bb_engine_get_tri_basis.argtypes = [c.c_void_p, _dp, _dp, _dp]
     L.bb_engine_set_tri_state.argtypes = [c.c_void_p, _dp]
@@ -210,6 +220,15 @@ def library(build: bool = True) -> ctypes.CDLL:
 
 def device_count() -> int:
     return int(library().bb_device_count())
+
+
+def compute_units(device: int = 0) -> int:
+    """Compute units of a device (a chain batch holds a fixed number of chains on each)."""
+    _require_gpu()
+    n = int(library().bb_compute_units(int(device)))
+    if n < 1:
+        raise RuntimeError(f"bayesbridge_amd: cannot query device {device}")
+    return n
 
 
 def _require_gpu():
@@ -509,6 +528,48 @@ def bridge_reg_tri(y, X, nsamp, alpha=0.5, sig2_shape=0.0, sig2_scale=0.0, nu_sh
                         d(tau_true), d(alpha), i(P), i(N), i(M), i(burn), ctypes.byref(rt),
                         i(1 if ortho else 0), i(betaburn), i(0))
     out = {k: v.T.copy() for k, v in tr.items()}
+    out.update(sig2=sig2, tau=tau, alpha=alph, runtime=rt.value)
+    return out
+
+
+def bridge_reg_tri_chains(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0, sig2_scale=0.0,
+                          nu_shape=2.0, nu_rate=2.0, alpha_a=1.0, alpha_b=1.0, sig2_true=0.0,
+                          tau_true=0.0, burn=500, ortho=False, betaburn=0):
+    """``nchains`` independent chains of bridge.reg.tri in one call, through
+    ``.C("bridge_regression_chains", ...)``: chain c is exactly what the c-th of ``nchains``
+    consecutive ``bridge_reg_tri`` calls would return.  Small designs (P <= 32, P <= N, alpha
+    known) run every chain side by side in one launch per block of sweeps, the SVD of X done
+    once.
+
+    Returns a dict: beta, u, w (omega), shape (K x M x P), sig2, tau, alpha (K x M), runtime
+    (one number for the batch).
+    """
+    L = library()
+    _require_gpu()
+    y = np.asarray(y, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    R, P = X.shape
+    N = y.shape[0]
+    M, K = int(nsamp), int(nchains)
+    if not check_parameters(N, R, M, sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                            alpha_b) or not _is_above(K, 1, "nchains"):
+        raise ValueError("bridge_reg_tri_chains: invalid parameters")
+    # P x M x K column-major is (K, M, P) in C order
+    out = {k: np.zeros((K, M, P)) for k in ("beta", "u", "w", "shape")}
+    sig2 = np.zeros((K, M))
+    tau = np.zeros((K, M))
+    alph = np.zeros((K, M))
+    d = lambda v: ctypes.byref(ctypes.c_double(float(v)))  # noqa: E731
+    i = lambda v: ctypes.byref(ctypes.c_int(int(v)))  # noqa: E731
+    rt = ctypes.c_double(0.0)
+    Xf = np.asfortranarray(X)
+    L.bridge_regression_chains(_p(out["beta"]), _p(out["u"]), _p(out["w"]), _p(out["shape"]),
+                               _p(sig2), _p(tau), _p(alph), _p(y), _p(Xf), d(sig2_shape),
+                               d(sig2_scale), d(nu_shape), d(nu_rate), d(alpha_a), d(alpha_b),
+                               d(sig2_true), d(tau_true), d(alpha), i(P), i(N), i(M), i(burn),
+                               ctypes.byref(rt), i(1 if ortho else 0), i(betaburn), i(0), i(K))
     out.update(sig2=sig2, tau=tau, alpha=alph, runtime=rt.value)
     return out
 
@@ -1210,7 +1271,9 @@ class Engine:
 class ChainBatch:
     """``nchains`` independent chains of one small dense design resident on one GPU, advanced
     together by one launch per run (bb_chains_*).  Chain c draws under the key
-    (cfg.seed, cfg.stream + c); cfg.trace_capacity is each chain's ring capacity."""
+    (cfg.seed, cfg.stream + c); cfg.trace_capacity is each chain's ring capacity.
+    cfg.method = 4 makes it a triangle-mixture batch (omega is the trace's ``lambda``; u and
+    shape through tri_trace / set_tri_state)."""
 
     def __init__(self, cfg: EngineConfig, nchains: int, X, y):
         L = library()
@@ -1265,6 +1328,36 @@ class ChainBatch:
         beta = np.ascontiguousarray(beta, dtype=np.float64)
         _check(library().bb_chains_set_state(self._h, int(chain), _p(beta), tau, sig2, alpha),
                "bb_chains_set_state")
+
+    def tri_trace(self, chain: int, slot0: int, count: int):
+        """Triangle method: u and shape traces of one chain (omega is ``trace()['lambda']``)."""
+        u = np.zeros((self.p, count), order="F")
+        shape = np.zeros((self.p, count), order="F")
+        _check(library().bb_chains_get_tri_trace(self._h, int(chain), slot0, count, _p(u),
+                                                 _p(shape)), "bb_chains_get_tri_trace")
+        return dict(u=u, shape=shape)
+
+    def set_tri_state(self, chain: int, u):
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        _check(library().bb_chains_set_tri_state(self._h, int(chain), _p(u)),
+               "bb_chains_set_tri_state")
+
+    def tri_basis(self):
+        """Triangle method: (tV, a, d) of the design the chains share, as Engine.tri_basis."""
+        p = self.p
+        tV = np.zeros((p, p), order="F")
+        a, d = np.zeros(p), np.zeros(p)
+        _check(library().bb_chains_get_tri_basis(self._h, _p(tV), _p(a), _p(d)),
+               "bb_chains_get_tri_basis")
+        return tV, a, d
+
+    def threads(self) -> int:
+        """Threads per workgroup of the kernel instance this batch runs."""
+        return int(library().bb_chains_threads(self._h))
+
+    def set_threads(self, threads: int):
+        """Triangle method: run another instance (A/B measurement; the results are the same)."""
+        _check(library().bb_chains_set_threads(self._h, int(threads)), "bb_chains_set_threads")
 
     def error_flags(self, chain: int) -> int:
         f = int(library().bb_chains_error_flags(self._h, int(chain)))

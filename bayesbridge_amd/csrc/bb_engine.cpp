@@ -1604,14 +1604,21 @@ void engine_init_state_local(bb_engine *e) {
     launch_record_scalars(e->stream, e->sc, e->tr_tau, e->tr_sig2, e->tr_alpha);
 }
 
-void engine_init_state(bb_engine *e) {
-    engine_init_state_local(e);
+// The draw a chain makes before burn-in, under the engine's current key (cfg.seed, cfg.stream)
+// and from the state engine_init_state_local left: one rule for a single engine and for every
+// chain of a batch (bb_chains::init_state), so the two cannot drift.
+void engine_preburn_draw(bb_engine *e) {
     if (e->method == 4 && e->cfg.ortho) {
         // triangle ortho driver draws sig2 then tau before burn-in (BridgeWrapper.cpp:374-375)
         if (!e->hy.know_tau || !e->hy.know_sig2) e->pre_and_scalars(0, 0, 0);
     } else if (e->method != 3 && !e->hy.know_tau) {
         e->pre_and_scalars(0, 0, 1);  // :262
     }
+}
+
+void engine_init_state(bb_engine *e) {
+    engine_init_state_local(e);
+    engine_preburn_draw(e);
     HIPCHECK(hipStreamSynchronize(e->stream));
 }
 
@@ -1644,8 +1651,16 @@ const char *chains_refusal(const bb_config &c) {
     if (c.n <= 0 || c.p <= 0) return "n and p must be positive";
     if (c.world > 1) return "a chain batch runs on one device (world == 1)";
     if (c.p_local > 0 && c.p_local != c.p) return "a chain batch holds every column (p_local == p)";
+    if (c.method == 4) {  // the triangle mixture: where bb_engine::fused runs k_tri_chain
+        static_assert(kTriChainMaxP == 32, "the message below says 32");
+        if (c.p > kTriChainMaxP) return "a triangle chain batch needs p <= 32";
+        if (c.p > c.n) return "a triangle chain batch needs p <= n";
+        if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
+        return nullptr;
+    }
     if (c.method != 0 && c.method != 1)
-        return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or 1)";
+        return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or "
+               "1) or the triangle mixture (method 4)";
     if (c.p > kSmallChainMaxP) return "a chain batch needs p <= 32";
     if (c.p > c.n && !c.ortho) return "a chain batch needs p <= n (or the orthogonal design)";
     if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
@@ -1655,10 +1670,12 @@ const char *chains_refusal(const bb_config &c) {
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Chain batch: K chains of one small design, a workgroup each (bb_small.hip k_small_chains).
-// One engine (`proto`, never run) holds what the chains share -- X, y, X'X, X'y and the
-// least-squares start -- and draws each chain's pre-burn tau under that chain's key; the
-// state, the error word and the trace rings are per chain ([chain][p], [chain][slot][p]).
+// Chain batch: K chains of one small design, a workgroup each (bb_small.hip k_small_chains;
+// the triangle mixture: bb_tri.hip k_tri_chains, with omega in lam).
+// One engine (`proto`, never run) holds what the chains share -- X, y, X'X, X'y, the
+// triangle mixture's SVD basis and the least-squares start -- and makes each chain's pre-burn
+// draw under that chain's key; the state, the error word and the trace rings are per chain
+// ([chain][p], [chain][slot][p]).
 // ---------------------------------------------------------------------------
 struct bb_chains {
     bb_engine *proto = nullptr;
@@ -1669,8 +1686,11 @@ struct bb_chains {
     uint32_t *err = nullptr;
     double *tr_beta = nullptr, *tr_lam = nullptr, *tr_sig2 = nullptr, *tr_tau = nullptr,
            *tr_alpha = nullptr;
+    // triangle mixture (proto->method == 4): u and shape beside omega (lam)
+    double *u = nullptr, *shape = nullptr, *tr_u = nullptr, *tr_shape = nullptr;
     Throttle ahead;
 
+    bool tri() const { return proto->method == 4; }
     ~bb_chains() {
         if (proto && proto->stream) (void)hipStreamSynchronize(proto->stream);
         for (void *q : owned) (void)hipFree(q);
@@ -1688,15 +1708,19 @@ struct bb_chains {
         e->cfg.stream = base_stream;
         engine_init_state_local(e);  // least-squares start, starting scalars, X beta
         HIPCHECK(hipMemcpyAsync(sc0, e->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
-        HIPCHECK(hipMemsetAsync(lam, 0, (size_t)K * pb, s));
-        const bool draw_tau = e->method != 3 && !e->hy.know_tau;
+        if (!tri()) HIPCHECK(hipMemsetAsync(lam, 0, (size_t)K * pb, s));
         for (int c = 0; c < K; ++c) {
             const size_t ring = (size_t)c * cap;
-            if (draw_tau) {  // BridgeWrapper.cpp:262 under the chain's own key
-                HIPCHECK(hipMemcpyAsync(e->sc, sc0, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
-                e->clear_err();
-                e->cfg.stream = base_stream + (uint64_t)c;
-                e->pre_and_scalars(0, 0, 1);
+            // the pre-burn draw under the chain's own key, from the shared starting scalars
+            HIPCHECK(hipMemcpyAsync(e->sc, sc0, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
+            e->clear_err();
+            e->cfg.stream = base_stream + (uint64_t)c;
+            engine_preburn_draw(e);
+            if (tri()) {  // u = 0.5, omega = 1 and their trace slot 0, as engine_init_state_local
+                HIPCHECK(hipMemcpyAsync(u + (size_t)c * p, e->u, pb, hipMemcpyDeviceToDevice, s));
+                HIPCHECK(hipMemcpyAsync(lam + (size_t)c * p, e->lam, pb, hipMemcpyDeviceToDevice, s));
+                HIPCHECK(hipMemcpyAsync(tr_u + ring * p, e->tr_u, pb, hipMemcpyDeviceToDevice, s));
+                HIPCHECK(hipMemcpyAsync(tr_lam + ring * p, e->tr_lam, pb, hipMemcpyDeviceToDevice, s));
             }
             HIPCHECK(hipMemcpyAsync(beta + (size_t)c * p, e->beta, pb, hipMemcpyDeviceToDevice, s));
             HIPCHECK(hipMemcpyAsync(sc + c, e->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
@@ -1717,6 +1741,15 @@ struct bb_chains {
 
     void run(uint64_t t0, int count, int first_slot, int slot_step) {
         bb_engine *e = proto;
+        if (tri()) {
+            if (launch_tri_chains(e->stream, K, threads, e->X, e->n_pad, e->n, e->p, e->y, e->tVc,
+                                  e->tVr, e->tri_a, e->tri_d, e->tri_G, e->cvec, e->cfg.ortho,
+                                  beta, u, lam, shape, sc, e->hy, e->cfg.betaburn, e->cfg.seed,
+                                  base_stream, t0, count, first_slot, slot_step, cap, tr_beta,
+                                  tr_u, tr_lam, tr_shape, tr_sig2, tr_tau, tr_alpha, err) != 0)
+                throw HipError("no triangle chain-batch instance of that many threads");
+            return;
+        }
         launch_small_chains(e->stream, K, e->X, e->n_pad, e->n, e->p, e->y, e->G, e->p_pad,
                             e->cvec, e->gdiag, e->method == 3, beta, lam, sc, e->hy, e->cfg.seed,
                             base_stream, t0, count, first_slot, slot_step, cap, tr_beta, tr_lam,
@@ -1728,7 +1761,7 @@ struct bb_chains {
     // Trace slots [slot0, slot0 + count) of EVERY chain -> samples [s0, s0 + count) of the
     // P x M x K (M x K) outputs: one strided copy per contiguous run of the ring and trace.
     void copy_out(int slot0, int count, int s0, int m, double *obeta, double *olam, double *osig2,
-                  double *otau, double *oalpha) {
+                  double *otau, double *oalpha, double *ou = nullptr, double *oshape = nullptr) {
         auto strided = [&](double *dst, const double *src, size_t w, int k, int sl, int run) {
             if (!dst) return;
             if (K == 1 || (run == cap && run == m)) {  // one contiguous block (no ring wrap)
@@ -1749,6 +1782,8 @@ struct bb_chains {
             strided(osig2, tr_sig2, 1, k, sl, run);
             strided(otau, tr_tau, 1, k, sl, run);
             strided(oalpha, tr_alpha, 1, k, sl, run);
+            strided(ou, tr_u, (size_t)p, k, sl, run);
+            strided(oshape, tr_shape, (size_t)p, k, sl, run);
             k += run;
         }
     }
@@ -1756,6 +1791,8 @@ struct bb_chains {
     uint64_t base_stream = 0;
     // the 256-thread instance (two chains per CU): bb_set_tuning key 21 and K >= 2 CUs
     int packed = 0;
+    // the triangle batch's instance, by its threads per workgroup (bb_chains_create)
+    int threads = 512;
 };
 
 // ---------------------------------------------------------------------------
@@ -1770,6 +1807,15 @@ int bb_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+
+int bb_compute_units(int device) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return cus;
 }
 
 void bb_set_seed(uint64_t seed) {
@@ -2294,11 +2340,14 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
         c.p_local = c.p;
         c.trace_capacity = 1;  // the shared engine records its own slot 0 only
         if (bb_engine_create(&c, X, y, &b->proto) != 0) throw HipError(g_last_error);
-        if (!b->proto->fused || b->proto->method == 4)
+        if (!b->proto->fused || (b->proto->method == 4) != (c.method == 4))
             throw HipError("this design does not run as a fused small chain");
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
-        b->packed = g_chains_packed && nchains >= 2 * cus;
+        b->packed = !b->tri() && g_chains_packed && nchains >= 2 * cus;
+        // more triangle chains than the 512-thread instance holds at once (one per CU): a
+        // narrower instance, several per CU, the same bits
+        if (b->tri()) b->threads = tri_chains_threads(c.n, c.p, nchains, cus);
         auto &o = b->owned;
         const size_t K = (size_t)nchains, p = (size_t)c.p, cap = (size_t)b->cap;
         b->beta = dalloc<double>(K * p, o);
@@ -2311,6 +2360,12 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
         b->tr_sig2 = dalloc<double>(K * cap, o);
         b->tr_tau = dalloc<double>(K * cap, o);
         b->tr_alpha = dalloc<double>(K * cap, o);
+        if (b->tri()) {
+            b->u = dalloc<double>(K * p, o);
+            b->shape = dalloc<double>(K * p, o);
+            b->tr_u = dalloc<double>(K * cap * p, o);
+            b->tr_shape = dalloc<double>(K * cap * p, o);
+        }
     } catch (std::exception &ex) {
         const std::string msg = ex.what();
         delete b;
@@ -2326,7 +2381,20 @@ int bb_chains_count(const bb_chains *b) { return b->K; }
 
 int bb_chains_resident_per_cu(const bb_chains *b) {
     if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
+    if (b->tri()) return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads);
     return small_chains_resident_per_cu(b->proto->n, b->p, b->packed);
+}
+
+int bb_chains_threads(const bb_chains *b) { return b->tri() ? b->threads : b->packed ? 256 : 512; }
+
+int bb_chains_set_threads(bb_chains *b, int threads) {
+    if (!b->tri() || hipSetDevice(b->proto->cfg.device) != hipSuccess ||
+        tri_chains_resident_per_cu(b->proto->n, b->p, threads) < 0) {
+        set_error("bb_chains_set_threads: no triangle chain-batch instance of %d threads", threads);
+        return -1;
+    }
+    b->threads = threads;
+    return 0;
 }
 
 int bb_chains_init_state(bb_chains *b) {
@@ -2431,6 +2499,51 @@ int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau,
         return -1;
     }
     return 0;
+}
+
+int bb_chains_get_tri_trace(bb_chains *b, int chain, int slot0, int count, double *u,
+                            double *shape) {
+    try {
+        b->check_chain(chain);
+        if (!b->tri()) throw HipError("not a triangle-method chain batch");
+        if (slot0 < 0 || count < 0)
+            throw HipError("bb_chains_get_tri_trace: slot0 and count must be >= 0");
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        const size_t pl = (size_t)b->p, ring = (size_t)chain * b->cap;
+        for (int k = 0; k < count;) {
+            const int s = (slot0 + k) % b->cap;
+            const int run = std::min(count - k, b->cap - s);
+            if (u) ring_copy(u + k * pl, b->tr_u + (ring + s) * pl, run * pl);
+            if (shape) ring_copy(shape + k * pl, b->tr_shape + (ring + s) * pl, run * pl);
+            k += run;
+        }
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_set_tri_state(bb_chains *b, int chain, const double *u) {
+    try {
+        b->check_chain(chain);
+        if (!b->tri()) throw HipError("not a triangle-method chain batch");
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        HIPCHECK(hipMemcpy(b->u + (size_t)chain * b->p, u, (size_t)b->p * sizeof(double),
+                           hipMemcpyHostToDevice));
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+    return 0;
+}
+
+int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d) {
+    if (!b->tri()) {
+        set_error("not a triangle-method chain batch");
+        return -1;
+    }
+    return bb_engine_get_tri_basis(b->proto, tV, a, d);
 }
 
 // ~0u when the flags cannot be read; bb_last_error then says why and is empty otherwise, which
@@ -4325,6 +4438,83 @@ Outcome tri_call(const bb_config &c, const double *yp, const double *Xp, int b, 
     return o;
 }
 
+// K triangle-mixture chains as one batch on tri_call's schedule (50-sweep blocks, `b` burn-in
+// sweeps, sample i at t = b + i).  The trace budget bounds the batch: each chain's ring gets a
+// K-th; a slot is 4 P-vectors (beta, u, omega, shape) and 3 scalars.
+Outcome tri_chains_batch(const bb_config &c0, int K, const double *yp, const double *Xp, int b,
+                         double *betap, double *up, double *omegap, double *shapep,
+                         double *sig2p, double *taup, double *alphap, double *runtime) {
+    const int m = c0.trace_capacity;
+    *runtime = 0.0;
+    bb_config c = c0;
+    {
+        const size_t per = (size_t)4 * c.p * sizeof(double) + 3 * sizeof(double);
+        size_t cap = g_trace_budget / (size_t)K / per;
+        if (cap < 16) cap = 16;
+        c.trace_capacity = (int)std::min<size_t>(cap, (size_t)(m < 1 ? 1 : m));
+    }
+    bb_chains *raw = nullptr;
+    if (bb_chains_create(&c, K, Xp, yp, &raw) != 0) return OUT_ERROR;
+    std::unique_ptr<bb_chains> ch(raw);
+    g_last_devices = 1;
+    g_last_capacity = ch->cap;
+    ChainsRun run{raw, ch->cap};
+    return drive_schedule(
+        run, 50, b, (uint64_t)b, m, b, runtime,
+        [&](int slot0, int count, int s0) {
+            ch->copy_out(slot0, count, s0, m, betap, omegap, sig2p, taup, alphap, up, shapep);
+            return 0;
+        },
+        [&] {
+            std::vector<uint32_t> f(K, 0u);
+            HIPCHECK(hipMemcpy(f.data(), ch->err, (size_t)K * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost));
+            for (int k = 0; k < K; ++k)
+                if (f[k] & ~4u) {
+                    printf("Error: numerical failure in the device sampler (flags %u) in chain "
+                           "%i\n", f[k], k);
+                    printf("Aborting Gibbs sampler.\n");
+                    fflush(stdout);
+                }
+        });
+}
+
+// bridge_regression_chains: the batch where the fused triangle chain applies, else the K
+// chains one after another through tri_call on streams k1 + c.
+Outcome tri_chains(const bb_config &c, int K, const double *yp, const double *Xp, int b,
+                   double *betap, double *up, double *omegap, double *shapep, double *sig2p,
+                   double *taup, double *alphap, double *runtime) {
+    const size_t m = (size_t)c.trace_capacity, pm = (size_t)c.p * m;
+    *runtime = 0.0;
+    if (chains_refusal(c) == nullptr) {
+        print_banner("Bridge Regression (mix. of triangles):", c, b, (int)m);
+        g_last_interrupted = 0;
+        const Outcome o = tri_chains_batch(c, K, yp, Xp, b, betap, up, omegap, shapep, sig2p,
+                                           taup, alphap, runtime);
+        if (o == OUT_ERROR) {
+            printf("Error: %s\n", g_last_error.c_str());
+            printf("Aborting Gibbs sampler.\n");
+            fflush(stdout);
+        }
+        if (g_verbose && o == OUT_OK)
+            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime,
+                   (int)m, K);
+        g_last_interrupted = o == OUT_INTERRUPTED;
+        return o;
+    }
+    for (int k = 0; k < K; ++k) {
+        bb_config ck = c;
+        ck.stream = c.stream + (uint64_t)k;
+        double rt = 0.0;
+        const Outcome o = tri_call(ck, yp, Xp, b, betap + k * pm, up + k * pm, omegap + k * pm,
+                                   shapep + k * pm, sig2p + k * m, taup + k * m, alphap + k * m,
+                                   &rt);
+        *runtime += rt;
+        if (o == OUT_INTERRUPTED) return o;
+    }
+    return OUT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4375,6 +4565,34 @@ void bridge_regression(double *betap, double *up, double *omegap, double *shapep
     c.betaburn = *betaburn > 0 ? *betaburn : 0;  // BridgeRegression.cpp:407
     if (tri_call(c, yp, Xp, *burn, betap, up, omegap, shapep, sig2p, taup, alphap, runtime) ==
         OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
+void bridge_regression_chains(double *betap, double *up, double *omegap, double *shapep,
+                              double *sig2p, double *taup, double *alphap, const double *yp,
+                              const double *Xp, const double *sig2_shape,
+                              const double *sig2_scale, const double *nu_shape,
+                              const double *nu_rate, const double *alpha_a,
+                              const double *alpha_b, const double *true_sig2,
+                              const double *true_tau, const double *true_alpha, const int *P,
+                              const int *N, const int *M, const int *burn, double *runtime,
+                              const int *ortho, const int *betaburn, const int *use_hmc,
+                              const int *nchains) {
+    (void)use_hmc;
+    if (*nchains < 1) {  // before a key is taken or an output is touched
+        set_error("bridge_regression_chains: nchains must be at least 1 (got %d)", *nchains);
+        printf("Error: %s\n", g_last_error.c_str());
+        fflush(stdout);
+        return;
+    }
+    const int no = 0;
+    bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
+                                     true_sig2, true_tau, true_alpha, *P, *N, *M, &no, *nchains);
+    c.method = 4;
+    c.ortho = *ortho != 0;
+    c.betaburn = *betaburn > 0 ? *betaburn : 0;
+    if (tri_chains(c, *nchains, yp, Xp, *burn, betap, up, omegap, shapep, sig2p, taup, alphap,
+                   runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 

@@ -418,6 +418,25 @@ void launch_tri_chain(hipStream_t s, const double *X, int ldx, int n, int p, con
                       double *tr_omega, double *tr_shape, double *tr_sig2, double *tr_tau,
                       double *tr_alpha, uint32_t *err);
 
+// The same sweeps for `nchains` independent chains in one launch, a workgroup per chain
+// (k_tri_chains): chain c has beta + c p (u, omega, shape alike), sc[c], err[c], the trace
+// rings tr_beta + c cap p (tr_sig2 + c cap, ...) and the key (k0, k1 + c); X, y, the basis (or
+// Gf, c), hy and betaburn are shared.  `threads` names the instance: 512 (the single chain's
+// LDS layout), or 256 or 128, which keep 512 virtual threads and size their LDS by p, so that
+// several chains share a CU; every instance gives the single chain's bits.  Returns -1
+// if there is no such instance.  tri_chains_resident_per_cu: the workgroups of that instance
+// the runtime keeps resident on one CU for an n x p design (-1 if the query fails).
+int launch_tri_chains(hipStream_t s, int nchains, int threads, const double *X, int ldx, int n,
+                      int p, const double *y, const double *tVc, const double *tVr,
+                      const double *a, const double *d, const double *Gf, const double *c,
+                      int ortho, double *beta, double *u, double *omega, double *shape,
+                      DevScalars *sc, Hyper hy, int betaburn, uint64_t k0, uint64_t k1,
+                      uint64_t t0, int count, int first_slot, int slot_step, int cap,
+                      double *tr_beta, double *tr_u, double *tr_omega, double *tr_shape,
+                      double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err);
+int tri_chains_resident_per_cu(int n, int p, int threads);
+int tri_chains_threads(int n, int p, int nchains, int cus);  // the instance a batch runs
+
 // Copy the scalars into trace slots (known parameters / alpha when known).
 void launch_record_scalars(hipStream_t s, const DevScalars *sc, double *tau_tr,
                            double *sig2_tr, double *alpha_tr);

@@ -65,12 +65,20 @@ __device__ __forceinline__ void attempt(Key key, uint64_t t, uint64_t i, uint64_
 // coordinate loop costs its prologue's s_waitcnt vmcnt(0), which drains the row prefetch
 // on every coordinate.  k0 > 0 resumes the rejection loop at attempt k0 (k_tri_chain's
 // fall-through after its parallel attempts; `pre` is then unused).
+// LOST (k_tri_chains): a standardised bound beyond ~1e154 overflows a * a, the threshold is
+// NaN and no attempt can be accepted; the draw then takes the loop's outcome (flag 64, the
+// bound itself) at once instead of after kTnMaxAttempts rounds on a CU other chains wait for.
+template <bool LOST = false>
 __device__ __forceinline__ double tn_pos(double a, double b, Key key, uint64_t t, uint64_t i,
                                          uint64_t it, const Pre &pre, uint32_t *err,
                                          long k0 = 0) {
     const double sq = sqrt(a * a + 4.0);
     const double as = 0.5 * (a + sq);
     const double thr = a + 2.0 / (a + sq) * exp(0.5 + 0.25 * (a * a - a * sq));
+    if (LOST && thr != thr) {
+        atomicOr(err, 64u);
+        return a;
+    }
     for (long k = k0; k < kTnMaxAttempts; ++k) {
         double r0, r1, x0;
         attempt(key, t, i, it, k, pre, r0, r1, x0, false);
@@ -87,6 +95,7 @@ __device__ __forceinline__ double tn_pos(double a, double b, Key key, uint64_t t
     return a;
 }
 
+template <bool LOST = false>
 __device__ __forceinline__ double tnorm(double lo, double hi, double mu, double sd, Key key,
                                         uint64_t t, uint64_t i, uint64_t it, const Pre &pre,
                                         uint32_t *err, long k0 = 0) {
@@ -110,15 +119,15 @@ __device__ __forceinline__ double tnorm(double lo, double hi, double mu, double 
         atomicOr(err, 64u);
         return lo;
     }
-    if (a > 0.0) return mu + sd * tn_pos(a, b, key, t, i, it, pre, err, k0);
-    return mu - sd * tn_pos(-b, -a, key, t, i, it, pre, err, k0);
+    if (a > 0.0) return mu + sd * tn_pos<LOST>(a, b, key, t, i, it, pre, err, k0);
+    return mu - sd * tn_pos<LOST>(-b, -a, key, t, i, it, pre, err, k0);
 }
 
 // The same draw with attempts 0 .. K-1 evaluated in parallel, attempt k in lane k from its
 // precomputed (r0, r1, x0): the lowest accepted attempt is the sequential loop's answer;
 // if none of the K is accepted the loop resumes at attempt K.  lo, hi, mu, sd uniform; every
 // lane of the wave calls this.
-template <int K>
+template <int K, bool LOST>
 __device__ __forceinline__ double tnorm_par(double lo, double hi, double mu, double sd,
                                             double r0, double r1, double x0, Key key,
                                             uint64_t t, uint64_t i, uint64_t it, uint32_t *err) {
@@ -157,7 +166,7 @@ __device__ __forceinline__ double tnorm_par(double lo, double hi, double mu, dou
     }
     const uint64_t m = __ballot(acc && lane < K);
     if (m) return readlane_dd(val, __ffsll((unsigned long long)m) - 1);
-    return tnorm(lo, hi, mu, sd, key, t, i, it, Pre{0.0, 0.0, 0.0}, err, K);
+    return tnorm<LOST>(lo, hi, mu, sd, key, t, i, it, Pre{0.0, 0.0, 0.0}, err, K);
 }
 
 // Row-of-16 max / min through DPP (quad xor 1, quad xor 2, half-row mirror, row mirror):
@@ -445,60 +454,95 @@ __device__ __forceinline__ double wave_sum64(double v) {
     return v;
 }
 
-struct TcVariates {  // counter-only variates of one sweep
-    double gt, gs;                 // Ga(tau shape, 1), Ga(sig2 shape, 1)
-    double om[kTcP][3], uu[kTcP];  // omega: r0 and the Ga(1, 1) / Ga(2, 1) variates; u
-    double r[kTcP][kTcK][2];       // attempt k of coordinate i (pass 0): r0, r1
-    double x[kTcP][kTcK];          //   and its Box-Muller normal
+// The counter-only variates of one sweep, in a buffer of tc_nvar(P) doubles laid out for P
+// coefficients (P = kTcP in the static buffers of the 512-thread instances, P = p in the
+// compact instance's dynamic LDS):
+//   [0] gt, [1] gs             Ga(tau shape, 1), Ga(sig2 shape, 1)
+//   om(j, 0..2), uu(j)         omega: r0 and the Ga(1, 1) / Ga(2, 1) variates; u
+//   r(i, k, 0..1), x(i, k)     attempt k of coordinate i (pass 0): r0, r1 and its Box-Muller normal
+struct TcVariates {
+    double *b;
+    int P;
+    __device__ __forceinline__ double &gt() const { return b[0]; }
+    __device__ __forceinline__ double &gs() const { return b[1]; }
+    __device__ __forceinline__ double &om(int j, int c) const { return b[2 + 3 * j + c]; }
+    __device__ __forceinline__ double &uu(int j) const { return b[2 + 3 * P + j]; }
+    __device__ __forceinline__ double &r(int i, int k, int c) const {
+        return b[2 + 4 * P + (i * kTcK + k) * 2 + c];
+    }
+    __device__ __forceinline__ double &x(int i, int k) const {
+        return b[2 + (4 + 2 * kTcK) * P + i * kTcK + k];
+    }
 };
+__host__ __device__ constexpr int tc_nvar(int P) { return 2 + (4 + 3 * kTcK) * P; }
 
 // Item e of sweep tt's variates (e < 2 + p (1 + kTcK)).
-__device__ __forceinline__ void tc_variate(TcVariates &v, int e, int p, double tau_shape,
+__device__ __forceinline__ void tc_variate(const TcVariates &v, int e, int p, double tau_shape,
                                            double sig2_shape, const Hyper &hy, Key key,
                                            uint64_t tt, uint32_t *err) {
     if (e == 0) {
-        if (!hy.know_tau) v.gt = gamma1(tau_shape, key, tt, KIND_TAU, err);
+        if (!hy.know_tau) v.gt() = gamma1(tau_shape, key, tt, KIND_TAU, err);
     } else if (e == 1) {
-        if (!hy.know_sig2) v.gs = gamma1(sig2_shape, key, tt, KIND_SIG2, err);
+        if (!hy.know_sig2) v.gs() = gamma1(sig2_shape, key, tt, KIND_SIG2, err);
     } else if (e < 2 + p) {
         const int j = e - 2;
         const U4 r = uniforms(key, tt, KIND_TRI_OMEGA, (uint64_t)j, 0, 0);
-        v.om[j][0] = r.r[0];
-        v.om[j][1] = -log(r.r[1]);                // Ga(1, 1)
-        v.om[j][2] = -log(r.r[1]) - log(r.r[2]);  // Ga(2, 1)
-        v.uu[j] = uniforms(key, tt, KIND_TRI_U, (uint64_t)j, 0, 0).r[0];
+        v.om(j, 0) = r.r[0];
+        v.om(j, 1) = -log(r.r[1]);                // Ga(1, 1)
+        v.om(j, 2) = -log(r.r[1]) - log(r.r[2]);  // Ga(2, 1)
+        v.uu(j) = uniforms(key, tt, KIND_TRI_U, (uint64_t)j, 0, 0).r[0];
     } else {
         const int q = e - 2 - p, i = q / kTcK, k = q % kTcK;
         const U4 r = uniforms(key, tt, KIND_TRI_Z, (uint64_t)i, 0, (uint64_t)k);
-        v.r[i][k][0] = r.r[0];
-        v.r[i][k][1] = r.r[1];
-        v.x[i][k] = bm_normal(r.r[0], r.r[1]);
+        v.r(i, k, 0) = r.r[0];
+        v.r(i, k, 1) = r.r[1];
+        v.x(i, k) = bm_normal(r.r[0], r.r[1]);
     }
 }
 
-__global__ __launch_bounds__(kTcNT) void k_tri_chain(
+// The whole sweep loop of one chain in one workgroup: k_tri_chain runs it once, k_tri_chains
+// once per workgroup on that chain's state, so the arithmetic exists once.
+// NT: real threads (64 | NT | kTcNT).  The only order-dependent arithmetic outside wave 0 is the
+// S_alpha / rss reduction over kTcNT threads; a narrower workgroup keeps kTcNT VIRTUAL threads,
+// real thread tid accumulating one separate partial for each virtual thread tid + q NT, so
+// every virtual wave lies in one real wave at the same lanes, its xor butterfly gives the same
+// bits and red[.][0..7] are summed in the same order.  The pre-drawn variates depend on their
+// counters alone, so which thread draws them does not matter.
+// COMPACT: the basis and the variate buffers live in the dynamic LDS behind X, sized by p
+// instead of kTcP, so that several workgroups share a CU's LDS.
+// LOST: a draw that can never be accepted gives up at once (tn_pos).
+template <int NT, bool COMPACT, bool LOST>
+__device__ __forceinline__ void tri_chain_body(
     const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
     const double *__restrict__ tVc, const double *__restrict__ tVr,
     const double *__restrict__ av, const double *__restrict__ dv, const double *__restrict__ Gf,
-    const double *__restrict__ cv, int ortho, int x_lds, double *beta,
-    double *u, double *omega, double *shape, DevScalars *sc, Hyper hy, int betaburn, Key key,
-    uint64_t t0, int count, int first_slot, int slot_step, int cap, double *tr_beta,
-    double *tr_u, double *tr_omega, double *tr_shape, double *tr_sig2, double *tr_tau,
-    double *tr_alpha, uint32_t *err) {
+    const double *__restrict__ cv, int ortho, int x_lds, double *beta, double *u, double *omega,
+    double *shape, DevScalars *sc, Hyper hy, int betaburn, Key key, uint64_t t0, int count,
+    int first_slot, int slot_step, int cap, double *tr_beta, double *tr_u, double *tr_omega,
+    double *tr_shape, double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err) {
+    static_assert(NT % 64 == 0 && NT >= 128 && kTcNT % NT == 0, "NT divides kTcNT; wave 1 draws sig2");
+    constexpr int Q = kTcNT / NT;  // virtual threads per real thread
     extern __shared__ double sX[];
-    __shared__ double sTc[kTcP * kTcP], sTr[kTcP * kTcP];
+    __shared__ double sT[COMPACT ? 1 : 2 * kTcP * kTcP];
+    __shared__ double sV[COMPACT ? 1 : 2 * tc_nvar(kTcP)];
     __shared__ double sb[kTcP];
-    __shared__ TcVariates vb[2];
     __shared__ double red[2][kTcNT / 64];
     __shared__ double s_tau, s_sig2;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    // variate buffers laid out for VP coefficients; COMPACT: [X | sTc | sTr | vb0 | vb1]
+    const int VP = COMPACT ? p : kTcP, TP = COMPACT ? p * p : kTcP * kTcP;
+    double *const dyn = sX + (x_lds ? (size_t)n * p : 0);
+    double *const sTc = COMPACT ? dyn : sT;
+    double *const sTr = sTc + TP;
+    double *const vbase = COMPACT ? dyn + 2 * TP : sV;
+    auto vbuf = [&](int half) { return TcVariates{vbase + half * tc_nvar(VP), VP}; };
     // orthogonal design: sTc holds the full symmetric Gram X'X (row j contiguous) instead
-    for (int e = tid; e < p * p; e += kTcNT) {
+    for (int e = tid; e < p * p; e += NT) {
         sTc[e] = ortho ? Gf[e] : tVc[e];
         if (!ortho) sTr[e] = tVr[e];
     }
     if (x_lds)
-        for (int e = tid; e < n * p; e += kTcNT) sX[e] = X[(size_t)(e % n) + (size_t)(e / n) * ldx];
+        for (int e = tid; e < n * p; e += NT) sX[e] = X[(size_t)(e % n) + (size_t)(e / n) * ldx];
     const double *Xs = x_lds ? sX : X;
     const int lds_x = x_lds ? n : ldx;
     const bool act = wid == 0 && lane < p;  // wave 0, lane j = coefficient / coordinate j
@@ -517,27 +561,35 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
     const double tau_shape = hy.nu_shape + ((double)p) / alpha;
     const double sig2_shape = hy.sig2_shape + 0.5 * (double)n;
     const int nvar = 2 + p * (1 + kTcK);
-    for (int e = tid; e < nvar; e += kTcNT)  // sweep 0's variates
-        tc_variate(vb[0], e, p, tau_shape, sig2_shape, hy, key, t0, err);
+    for (int e = tid; e < nvar; e += NT)  // sweep 0's variates
+        tc_variate(vbuf(0), e, p, tau_shape, sig2_shape, hy, key, t0, err);
     __syncthreads();
     for (int k = 0; k < count; ++k) {
-        TcVariates &v = vb[k & 1];
+        const TcVariates v = vbuf(k & 1);
         const uint64_t t = t0 + (uint64_t)k;
         const int slot = first_slot < 0 ? -1 : (first_slot + k * slot_step) % cap;
         // ---- S_alpha = sum |beta_j|^alpha and rss = |y - X beta|^2 ----
-        double sa = 0.0, rs = 0.0;
+        // (p <= 64: only virtual wave 0 holds terms of S_alpha, the others' sums are +0)
+        double sa = 0.0, rs[Q];
         if (tid < p) sa = exp(alpha * log(fabs(sb[tid])));
-        for (int i = tid; i < n; i += kTcNT) {
-            double xb = 0.0;
-            for (int j = 0; j < p; ++j) xb += Xs[(size_t)i + (size_t)j * lds_x] * sb[j];
-            const double r = y[i] - xb;
-            rs += r * r;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            rs[q] = 0.0;
+            for (int i = tid + q * NT; i < n; i += kTcNT) {
+                double xb = 0.0;
+                for (int j = 0; j < p; ++j) xb += Xs[(size_t)i + (size_t)j * lds_x] * sb[j];
+                const double r = y[i] - xb;
+                rs[q] += r * r;
+            }
         }
         sa = wave_sum64(sa);
-        rs = wave_sum64(rs);
-        if (lane == 0) {
-            red[0][wid] = sa;
-            red[1][wid] = rs;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            rs[q] = wave_sum64(rs[q]);
+            if (lane == 0) {
+                red[0][wid + q * (NT / 64)] = q == 0 ? sa : 0.0;
+                red[1][wid + q * (NT / 64)] = rs[q];
+            }
         }
         __syncthreads();
         // tau | beta (wave 0) and sig2 | beta (wave 1), as k_scalars
@@ -546,13 +598,13 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
 #pragma unroll
             for (int w = 1; w < kTcNT / 64; ++w) S += red[tid == 0 ? 0 : 1][w];
             if (tid == 0) {
-                if (!hy.know_tau) s_tau = exp(-1.0 * log(v.gt / (hy.nu_rate + S)) / alpha);
+                if (!hy.know_tau) s_tau = exp(-1.0 * log(v.gt() / (hy.nu_rate + S)) / alpha);
                 if (slot >= 0) {
                     tr_tau[slot] = s_tau;
                     tr_alpha[slot] = alpha;
                 }
             } else {
-                if (!hy.know_sig2) s_sig2 = (hy.sig2_scale + 0.5 * S) / v.gs;
+                if (!hy.know_sig2) s_sig2 = (hy.sig2_scale + 0.5 * S) / v.gs();
                 if (slot >= 0) tr_sig2[slot] = s_sig2;
             }
         }
@@ -560,8 +612,8 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
         if (wid > 0) {
             // the next sweep's variates, off wave 0's serial chain
             if (k + 1 < count)
-                for (int e = tid - 64; e < nvar; e += kTcNT - 64)
-                    tc_variate(vb[(k + 1) & 1], e, p, tau_shape, sig2_shape, hy, key, t + 1, err);
+                for (int e = tid - 64; e < nvar; e += NT - 64)
+                    tc_variate(vbuf((k + 1) & 1), e, p, tau_shape, sig2_shape, hy, key, t + 1, err);
         } else {
             const double tau = s_tau, sig2 = s_sig2, sig = sqrt(sig2);
             double bj = 0.0;
@@ -572,17 +624,22 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
                 const double aj = exp(alpha * log(fabs(betaj) / ((1.0 - uj) * tau)));
                 const double prob = alpha / (1.0 + alpha * aj);
                 double w;
-                if (v.om[lane][0] > prob) {
+                if (v.om(lane, 0) > prob) {
                     sh = 1.0;
-                    w = v.om[lane][1];
+                    w = v.om(lane, 1);
                 } else {
                     sh = 2.0;
-                    w = v.om[lane][2];
+                    w = v.om(lane, 2);
                 }
                 om = w + aj;
                 const double right = 1.0 - fabs(betaj) / tau * exp(-1.0 * log(om) / alpha);
-                uj = right * v.uu[lane];
+                uj = right * v.uu(lane);
                 bj = (1.0 - uj) * exp(log(om) / alpha) * tau;
+                // A NaN bound (the chain's state is no longer finite) is no truncation
+                // interval.  The orthogonal pass reports it (tnorm's flag 128); the general
+                // pass would draw NaN after NaN from the flat branch below without a word,
+                // so a batch reports it here, in the chain's own flag word.
+                if (LOST && bj != bj) atomicOr(err, 128u);
                 if (slot >= 0) {
                     tr_omega[(size_t)slot * p + lane] = om;
                     tr_shape[(size_t)slot * p + lane] = sh;
@@ -603,9 +660,9 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
                     const double m = (readlane_d(aj_c, j) - xb) / gjj;
                     const double sd = sqrt(sig2 / gjj);
                     const int ka = lane < kTcK ? lane : 0;
-                    const double zn = tnorm_par<kTcK>(-1.0 * bnd, bnd, m, sd, v.r[j][ka][0],
-                                                      v.r[j][ka][1], v.x[j][ka], key, t,
-                                                      (uint64_t)j, 0, err);
+                    const double zn = tnorm_par<kTcK, LOST>(-1.0 * bnd, bnd, m, sd, v.r(j, ka, 0),
+                                                            v.r(j, ka, 1), v.x(j, ka), key, t,
+                                                            (uint64_t)j, 0, err);
                     if (lane == j) bl = zn;
                 }
                 if (act) {
@@ -653,17 +710,17 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
                     if (it == 0) {
                         const int ka = lane < kTcK ? lane : 0;
                         if (sdi > 0.0)
-                            zn = tnorm_par<kTcK>(L, R, readlane_d(ci, i), sdi, v.r[i][ka][0],
-                                                 v.r[i][ka][1], v.x[i][ka], key, t, (uint64_t)i,
-                                                 0, err);
+                            zn = tnorm_par<kTcK, LOST>(L, R, readlane_d(ci, i), sdi,
+                                                       v.r(i, ka, 0), v.r(i, ka, 1), v.x(i, ka),
+                                                       key, t, (uint64_t)i, 0, err);
                         else
-                            zn = L + (R - L) * v.r[i][0][0];
+                            zn = L + (R - L) * v.r(i, 0, 0);
                     } else {
                         const Pre pi{readlane_d(pr.r0, i), readlane_d(pr.r1, i),
                                      readlane_d(pr.x0, i)};
                         if (sdi > 0.0)
-                            zn = tnorm(L, R, readlane_d(ci, i), sdi, key, t, (uint64_t)i,
-                                       (uint64_t)it, pi, err);
+                            zn = tnorm<LOST>(L, R, readlane_d(ci, i), sdi, key, t, (uint64_t)i,
+                                             (uint64_t)it, pi, err);
                         else
                             zn = L + (R - L) * pi.r0;
                     }
@@ -694,6 +751,48 @@ __global__ __launch_bounds__(kTcNT) void k_tri_chain(
         sc->tau = s_tau;
         sc->sig2 = s_sig2;
     }
+}
+
+__global__ __launch_bounds__(kTcNT) void k_tri_chain(
+    const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
+    const double *__restrict__ tVc, const double *__restrict__ tVr,
+    const double *__restrict__ av, const double *__restrict__ dv, const double *__restrict__ Gf,
+    const double *__restrict__ cv, int ortho, int x_lds, double *beta,
+    double *u, double *omega, double *shape, DevScalars *sc, Hyper hy, int betaburn, Key key,
+    uint64_t t0, int count, int first_slot, int slot_step, int cap, double *tr_beta,
+    double *tr_u, double *tr_omega, double *tr_shape, double *tr_sig2, double *tr_tau,
+    double *tr_alpha, uint32_t *err) {
+    tri_chain_body<kTcNT, false, false>(X, ldx, n, p, y, tVc, tVr, av, dv, Gf, cv, ortho, x_lds,
+                                        beta, u, omega, shape, sc, hy, betaburn, key, t0, count,
+                                        first_slot, slot_step, cap, tr_beta, tr_u, tr_omega,
+                                        tr_shape, tr_sig2, tr_tau, tr_alpha, err);
+}
+
+// K independent chains, one workgroup each (blockIdx.x = chain c): the design, the basis (or
+// Gf, cv), the hyper-parameters and betaburn are shared and read-only; the state (beta, u,
+// omega, shape: stride p; sc, err: one per chain), the trace rings ([chain][slot][p],
+// [chain][slot]) and the Philox key (key.k0, key.k1 + c) are the chain's own.  No workgroup
+// waits for another, so K may exceed what the device holds at once.
+// (two waves per SIMD: at most 256 VGPRs, what the 512-thread single chain is built with, so
+// that 512 / NT workgroups share a CU's registers)
+template <int NT, bool COMPACT>
+__global__ __launch_bounds__(NT, 2) void k_tri_chains(
+    const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
+    const double *__restrict__ tVc, const double *__restrict__ tVr,
+    const double *__restrict__ av, const double *__restrict__ dv, const double *__restrict__ Gf,
+    const double *__restrict__ cv, int ortho, int x_lds, double *beta,
+    double *u, double *omega, double *shape, DevScalars *sc, Hyper hy, int betaburn, Key key,
+    uint64_t t0, int count, int first_slot, int slot_step, int cap, double *tr_beta,
+    double *tr_u, double *tr_omega, double *tr_shape, double *tr_sig2, double *tr_tau,
+    double *tr_alpha, uint32_t *err) {
+    const size_t c = blockIdx.x;
+    const Key ck{key.k0, key.k1 + (uint64_t)c};
+    const size_t ring = c * (size_t)cap;
+    tri_chain_body<NT, COMPACT, true>(
+        X, ldx, n, p, y, tVc, tVr, av, dv, Gf, cv, ortho, x_lds, beta + c * p, u + c * p,
+        omega + c * p, shape + c * p, sc + c, hy, betaburn, ck, t0, count, first_slot, slot_step,
+        cap, tr_beta + ring * p, tr_u + ring * p, tr_omega + ring * p, tr_shape + ring * p,
+        tr_sig2 + ring, tr_tau + ring, tr_alpha + ring, err + c);
 }
 
 // Truncated normal / exponential batches behind the .C utilities rtnorm_left, rtnorm_both,
@@ -857,6 +956,96 @@ void launch_tri_chain(hipStream_t s, const double *X, int ldx, int n, int p, con
         X, ldx, n, p, y, tVc, tVr, a, d, Gf, c, ortho, x_lds, beta, u, omega, shape, sc, hy, betaburn,
         Key{k0, k1}, t0, count, first_slot, slot_step, cap, tr_beta, tr_u, tr_omega, tr_shape,
         tr_sig2, tr_tau, tr_alpha, err);
+}
+
+namespace {
+
+using TriChainsKernel = decltype(&k_tri_chains<kTcNT, false>);
+struct TriChainsInstance {
+    TriChainsKernel kern;
+    int nt;
+    bool compact;
+};
+
+// The batch instance of `threads` threads (nullptr: none), its >64 KB LDS opt-in made once.
+const TriChainsInstance *tri_chains_instance(int threads) {
+    static const TriChainsInstance inst[] = {{k_tri_chains<kTcNT, false>, kTcNT, false},
+                                             {k_tri_chains<256, true>, 256, true},
+                                             {k_tri_chains<128, true>, 128, true}};
+    static const bool optin = [] {
+        for (const TriChainsInstance &i : inst) {
+            const size_t extra =
+                i.compact ? (2 * kTcP * kTcP + 2 * tc_nvar(kTcP)) * sizeof(double) : 0;
+            (void)hipFuncSetAttribute((const void *)i.kern,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)(kTcXLds + extra));
+        }
+        return true;
+    }();
+    (void)optin;
+    for (const TriChainsInstance &i : inst)
+        if (i.nt == threads) return &i;
+    return nullptr;
+}
+
+// dynamic LDS of a launch: X when it fits under kTcXLds, and for a compact instance the basis
+// and the two variate buffers behind it, all sized by p
+size_t tri_chains_shm(const TriChainsInstance &i, int n, int p, int *x_lds) {
+    const size_t xbytes = (size_t)n * p * sizeof(double);
+    *x_lds = xbytes <= kTcXLds;
+    const size_t extra = i.compact ? (2 * (size_t)p * p + 2 * tc_nvar(p)) * sizeof(double) : 0;
+    return (*x_lds ? xbytes : 0) + extra;
+}
+
+}  // namespace
+
+int launch_tri_chains(hipStream_t s, int nchains, int threads, const double *X, int ldx, int n,
+                      int p, const double *y, const double *tVc, const double *tVr,
+                      const double *a, const double *d, const double *Gf, const double *c,
+                      int ortho, double *beta, double *u, double *omega, double *shape,
+                      DevScalars *sc, Hyper hy, int betaburn, uint64_t k0, uint64_t k1,
+                      uint64_t t0, int count, int first_slot, int slot_step, int cap,
+                      double *tr_beta, double *tr_u, double *tr_omega, double *tr_shape,
+                      double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err) {
+    const TriChainsInstance *inst = tri_chains_instance(threads);
+    if (!inst || p < 1 || p > kTriChainMaxP) return -1;  // the batch checks both at creation
+    if (count <= 0 || nchains <= 0) return 0;
+    int x_lds = 0;
+    const size_t shm = tri_chains_shm(*inst, n, p, &x_lds);
+    inst->kern<<<nchains, inst->nt, shm, s>>>(
+        X, ldx, n, p, y, tVc, tVr, a, d, Gf, c, ortho, x_lds, beta, u, omega, shape, sc, hy,
+        betaburn, Key{k0, k1}, t0, count, first_slot, slot_step, cap, tr_beta, tr_u, tr_omega,
+        tr_shape, tr_sig2, tr_tau, tr_alpha, err);
+    return 0;
+}
+
+// The instance for a batch of `nchains` on a device of `cus` compute units: the widest one
+// that holds every chain at once (a wider workgroup leaves wave 0 more of its SIMD), else the
+// one that holds the most.  Every instance gives the same bits, so this is a matter of speed
+// alone.
+int tri_chains_threads(int n, int p, int nchains, int cus) {
+    int best = kTcNT, best_r = 0;
+    for (int nt : {kTcNT, 256, 128}) {
+        const int r = tri_chains_resident_per_cu(n, p, nt);
+        if (r <= best_r) continue;
+        best = nt;
+        best_r = r;
+        if ((long)nchains <= (long)r * cus) break;
+    }
+    return best;
+}
+
+int tri_chains_resident_per_cu(int n, int p, int threads) {
+    const TriChainsInstance *inst = tri_chains_instance(threads);
+    if (!inst) return -1;
+    int x_lds = 0, blocks = 0;
+    const size_t shm = tri_chains_shm(*inst, n, p, &x_lds);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)inst->kern, inst->nt,
+                                                     shm) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return blocks;
 }
 
 }  // namespace bb

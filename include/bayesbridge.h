@@ -156,6 +156,9 @@ void bridge_reg_logit(double *betap, double *lambdap, double *taup, double *alph
 const char *bb_version(void);
 const char *bb_last_error(void);
 int bb_device_count(void);
+/* Compute units of device `device` (-1 if it cannot be queried): a chain batch holds a fixed
+ * number of chains per compute unit (bb_chains_resident_per_cu). */
+int bb_compute_units(int device);
 
 /*
  * RNG seeding.  Every variate is Philox4x64-10 of a counter; the key
@@ -275,6 +278,20 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
  * (With bb_set_tuning key 21 set, a batch of at least 2 x compute units chains runs the
  * two-per-CU instance, which is not bit for bit the single engine's chain; see there.)
  *
+ * The triangle mixture (cfg->method == 4; bb_tri.hip k_tri_chains) runs as a batch wherever a
+ * single engine runs k_tri_chain fused: p <= 32, p <= n, world == 1, alpha known, either
+ * `ortho` value, any `betaburn`.  The SVD basis (or the Gram, for the orthogonal design) is
+ * computed once for the batch.  omega is the batch's `lambda`; u and shape have the calls
+ * bb_chains_get_tri_trace, bb_chains_set_tri_state and bb_chains_get_tri_basis, which mean for
+ * chain `chain` what the bb_engine_* calls of those names mean.  A batch of more chains than
+ * the device has compute units runs a 256-thread instance of the kernel (two chains per
+ * compute unit), one of more than twice as many a 128-thread instance (up to four); both keep
+ * the 512-thread instance's order of every sum, so a triangle chain is bit for bit the single
+ * engine's chain at every batch size and no tuning key selects them.
+ * bb_chains_threads reports the threads per workgroup of the batch's instance;
+ * bb_chains_set_threads picks another instance of a triangle batch for A/B measurement (512,
+ * 256 or 128; -1 if there is none) -- never a change of results.
+ *
  * init_state, run, sync, get_trace, get_state and set_state mean for chain `chain` what the
  * bb_engine_* calls mean for a single engine; bb_chains_run advances every chain by `count`
  * sweeps.  bb_chains_error_flags returns chain `chain`'s flag word (a failed Cholesky pivot
@@ -301,6 +318,12 @@ int bb_chains_get_state(bb_chains *b, int chain, double *beta, double *lambda, d
 int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau, double sig2,
                         double alpha);
 unsigned bb_chains_error_flags(bb_chains *b, int chain);
+int bb_chains_get_tri_trace(bb_chains *b, int chain, int slot0, int count, double *u,
+                            double *shape);
+int bb_chains_set_tri_state(bb_chains *b, int chain, const double *u);
+int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d);
+int bb_chains_threads(const bb_chains *b);
+int bb_chains_set_threads(bb_chains *b, int threads);
 
 /*
  * K independent chains of bridge_reg_stable in one call: the arguments of bridge_reg_stable
@@ -323,6 +346,30 @@ void bridge_reg_stable_chains(double *betap, double *lambdap, double *sig2p, dou
                               const double *true_alpha, const int *P, const int *N,
                               const int *M, const int *burn, double *runtime,
                               const int *ortho, const int *nchains);
+
+/*
+ * K independent chains of bridge_regression (the triangle mixture) in one call: its 26
+ * arguments with `nchains` appended.  betap, up, omegap and shapep are P x M x K column-major,
+ * sig2p, taup and alphap are M x K; runtime is one number for the batch.  Chain c returns
+ * exactly what the c-th of K consecutive bridge_regression calls would return: one call key
+ * is taken and chain c draws under (k0, k1 + c) (outside R the stream counter advances by K).
+ * Designs a triangle chain batch accepts (bb_chains_create: p <= 32, alpha known) run as one
+ * batch on bridge_regression's schedule, the SVD of X done once, with the trace budget
+ * bounding the rings of the whole batch (a slot is 4 P-vectors and 3 scalars); every other
+ * design bridge_regression accepts runs its K chains one after another.  Chains with a
+ * numerical failure are reported per chain.  nchains < 1 prints an error and returns before
+ * a key is taken or an output is written.
+ */
+void bridge_regression_chains(double *betap, double *up, double *omegap, double *shapep,
+                              double *sig2p, double *taup, double *alphap, const double *yp,
+                              const double *Xp, const double *sig2_shape,
+                              const double *sig2_scale, const double *nu_shape,
+                              const double *nu_rate, const double *alpha_a,
+                              const double *alpha_b, const double *true_sig2,
+                              const double *true_tau, const double *true_alpha, const int *P,
+                              const int *N, const int *M, const int *burn, double *runtime,
+                              const int *ortho, const int *betaburn, const int *use_hmc,
+                              const int *nchains);
 
 /*
  * Shard group: `count` engines with cfg.rank = 0..count-1 and cfg.world = count, each

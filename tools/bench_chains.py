@@ -9,6 +9,11 @@ kernel-only rate (ChainBatch.run without traces) separates the sweeps from the c
 K = 2 CUs and 4 CUs are measured a second time with bb_set_tuning key 21 (the 256-thread
 instance, two chains per CU) into the record's "chains_two_per_cu".
 
+--method tri measures the triangle mixture instead (bridge_reg_tri_chains, bb_tri.hip
+k_tri_chains) into profiles/chains_tri_{c1,db}.json.  Its instances all give the same bits, so
+there is no tuning key: the record's "instances" holds the kernel-only rate of every instance
+(ChainBatch.set_threads) at K = CUs, 2 CUs and 4 CUs, alternated within each round.
+
 Protocol: one warm-up call, then REPS rounds, each round visiting every K (and the
 single-chain bridge_reg_stb call) once, so slow drifts of the device hit every K alike; the
 median over rounds is reported with the min and max beside it.
@@ -16,6 +21,7 @@ median over rounds is reported with the min and max beside it.
   python tools/bench_chains.py                 # both designs -> profiles/chains_{c1,db}.json
   python tools/bench_chains.py --mode single --tree DIR   # bridge_reg_stb alone, from the
                                                           # checkout at DIR (A/B with a parent)
+  python tools/bench_chains.py --method tri [--mode single --tree DIR]
 """
 import argparse
 import json
@@ -44,16 +50,39 @@ def designs():
     return out
 
 
+class Method:
+    """The entry points of one sampler: stable mixture or triangle mixture."""
+
+    def __init__(self, bb, name):
+        self.bb, self.tri = bb, name == "tri"
+
+    def single(self, y, X, **kw):
+        if self.tri:
+            return self.bb.bridge_reg_tri(y, X, extras=True, **kw)
+        return self.bb.bridge_reg_stb(y, X, **kw)
+
+    def chains(self, y, X, **kw):
+        return (self.bb.bridge_reg_tri_chains if self.tri
+                else self.bb.bridge_reg_stb_chains)(y, X, **kw)
+
+    def config(self, n, p):
+        return self.bb.EngineConfig(n=n, p=p, trace_capacity=1, seed=SEED,
+                                    method=4 if self.tri else 0)
+
+
 def spread(v):
     v = sorted(v)
     return {"median": float(np.median(v)), "min": float(v[0]), "max": float(v[-1])}
 
 
-def kernel_rate(bb, X, y, K, nsamp):
-    """Sweeps/s of the batch kernel alone: blocks of 50 sweeps, no traces, one sync."""
+def kernel_rate(me, X, y, K, nsamp, threads=0):
+    """Sweeps/s of the batch kernel alone: blocks of 50 sweeps, no traces, one sync.
+    threads: the triangle batch's instance (0: the one the batch selects)."""
     n, p = X.shape
-    b = bb.ChainBatch(bb.EngineConfig(n=n, p=p, trace_capacity=1, seed=SEED), K, X, y)
+    b = me.bb.ChainBatch(me.config(n, p), K, X, y)
     try:
+        if threads:
+            b.set_threads(threads)
         b.init_state()
         b.run(1, 500, 0, 0, 0)
         b.sync()
@@ -67,10 +96,11 @@ def kernel_rate(bb, X, y, K, nsamp):
         b.close()
 
 
-def single_kernel_rate(bb, X, y, nsamp):
-    """kernel_rate for one bb.Engine (k_small_chain): the batch kernel's K = 1 counterpart."""
+def single_kernel_rate(me, X, y, nsamp):
+    """kernel_rate for one bb.Engine (k_small_chain / k_tri_chain): the batch kernel's K = 1
+    counterpart."""
     n, p = X.shape
-    e = bb.Engine(bb.EngineConfig(n=n, p=p, trace_capacity=1, seed=SEED), X, y)
+    e = me.bb.Engine(me.config(n, p), X, y)
     try:
         e.init_state()
         e.run(1, 500, 0, 0, 0)
@@ -84,31 +114,38 @@ def single_kernel_rate(bb, X, y, nsamp):
         e.close()
 
 
-def bench_design(bb, name, X, y, cus, args, Ks=None):
+def bench_design(me, name, X, y, cus, args, Ks=None):
+    bb = me.bb
     Ks = Ks or [k for k in dict.fromkeys([1, 8, 64, cus, 2 * cus, 4 * cus])
                 if k <= args.max_chains]
     nsamp, burn = args.nsamp, args.burn
     bb.set_seed(SEED)
-    bb.bridge_reg_stb_chains(y, X, nsamp=200, nchains=2, burn=100)  # warm-up
-    bb.bridge_reg_stb(y, X, nsamp=200, burn=100)
+    me.chains(y, X, nsamp=200, nchains=2, burn=100)  # warm-up
+    me.single(y, X, nsamp=200, burn=100)
+    big = [k for k in (cus, 2 * cus, 4 * cus) if k <= args.max_chains] if me.tri else []
+    inst = {(K, t): [] for K in big for t in args.instances}
+    inst_res = {}
     rt = {K: [] for K in Ks}
     wall = {K: [] for K in Ks}
     kern = {K: [] for K in Ks}
     single, single_kern = [], []
-    res = None
+    res = {}
     for _ in range(args.reps):
         bb.set_seed(SEED)
-        single.append(nsamp / bb.bridge_reg_stb(y, X, nsamp=nsamp, burn=burn)["runtime"])
-        single_kern.append(single_kernel_rate(bb, X, y, nsamp))
+        single.append(nsamp / me.single(y, X, nsamp=nsamp, burn=burn)["runtime"])
+        single_kern.append(single_kernel_rate(me, X, y, nsamp))
         for K in Ks:
             bb.set_seed(SEED)
             t0 = time.perf_counter()
-            out = bb.bridge_reg_stb_chains(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            out = me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn)
             wall[K].append(time.perf_counter() - t0)
             rt[K].append(out["runtime"])
             del out
-            kr, res = kernel_rate(bb, X, y, K, nsamp)
+            kr, res[K] = kernel_rate(me, X, y, K, nsamp)
             kern[K].append(kr)
+        for K, t in inst:  # the instances side by side, every round
+            kr, inst_res[K, t] = kernel_rate(me, X, y, K, nsamp, t)
+            inst[K, t].append(kr)
     rows = []
     for K in Ks:
         agg = [K * nsamp / r for r in rt[K]]
@@ -116,7 +153,7 @@ def bench_design(bb, name, X, y, cus, args, Ks=None):
                      "aggregate_sweeps_per_s": spread(agg),
                      "per_chain_sweeps_per_s": spread([a / K for a in agg]),
                      "kernel_aggregate_sweeps_per_s": spread(kern[K]),
-                     "resident_per_cu": res})
+                     "resident_per_cu": res[K]})
     one = rows[0]["aggregate_sweeps_per_s"]["median"]
     for r in rows:
         r["aggregate_vs_one_chain"] = r["aggregate_sweeps_per_s"]["median"] / one
@@ -126,31 +163,37 @@ def bench_design(bb, name, X, y, cus, args, Ks=None):
            "burn": burn, "reps": args.reps, "compute_units": cus,
            "single_call_sweeps_per_s": spread(single),
            "single_kernel_sweeps_per_s": spread(single_kern), "chains": rows}
-    if name == "c1":
+    if inst:
+        rec["instances"] = [{"chains": K, "threads": t, "resident_per_cu": inst_res[K, t],
+                             "kernel_aggregate_sweeps_per_s": spread(v)}
+                            for (K, t), v in inst.items()]
+    if name == "c1" and not me.tri:
         best = max(r["aggregate_sweeps_per_s"]["median"] for r in rows)
         rec["cpu_core_sweeps_per_s"] = CPU_CORE_C1
         rec["cpu_cores_worth"] = best / CPU_CORE_C1
     return rec
 
 
-def bench_single(bb, args):
-    """bridge_reg_stb alone at both designs (one JSON line): the A/B against another checkout."""
+def bench_single(me, args):
+    """The single-chain call alone at both designs (one JSON line): the A/B against another
+    checkout."""
     out = {}
     for name, (X, y) in designs().items():
-        bb.set_seed(SEED)
-        bb.bridge_reg_stb(y, X, nsamp=200, burn=100)
+        me.bb.set_seed(SEED)
+        me.single(y, X, nsamp=200, burn=100)
         v = []
         for _ in range(args.reps):
-            bb.set_seed(SEED)
-            v.append(args.nsamp / bb.bridge_reg_stb(y, X, nsamp=args.nsamp,
-                                                    burn=args.burn)["runtime"])
+            me.bb.set_seed(SEED)
+            v.append(args.nsamp / me.single(y, X, nsamp=args.nsamp, burn=args.burn)["runtime"])
         out[name] = spread(v)
-    print(json.dumps({"tree": args.tree, "single_call_sweeps_per_s": out}), flush=True)
+    print(json.dumps({"tree": args.tree, "method": args.method,
+                      "single_call_sweeps_per_s": out}), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--mode", choices=["chains", "single"], default="chains")
+    ap.add_argument("--method", choices=["stable", "tri"], default="stable")
     ap.add_argument("--tree", default=ROOT, help="checkout whose bayesbridge_amd is measured")
     ap.add_argument("--designs", default="c1,db")
     ap.add_argument("--nsamp", type=int, default=5000)
@@ -159,6 +202,8 @@ def main():
     ap.add_argument("--max-chains", type=int, default=1 << 20)
     ap.add_argument("--tuning", default="",
                     help="KEY=VALUE,...: bb_set_tuning before measuring (A/B of a variant build)")
+    ap.add_argument("--instances", type=lambda v: [int(t) for t in v.split(",")],
+                    default=[512, 256, 128], help="triangle batch instances to compare (threads)")
     ap.add_argument("--tag", default="", help="suffix of the output files' names")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
@@ -171,23 +216,26 @@ def main():
     for kv in filter(None, args.tuning.split(",")):
         k, v = kv.split("=")
         bb.set_tuning(int(k), int(v))
+    me = Method(bb, args.method)
     if args.mode == "single":
-        return bench_single(bb, args)
-    cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+        return bench_single(me, args)
+    cus = (bb.compute_units() if hasattr(bb, "compute_units")
+           else int(torch.cuda.get_device_properties(0).multi_processor_count))
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
             continue
-        rec = bench_design(bb, name, X, y, cus, args)
+        rec = bench_design(me, name, X, y, cus, args)
         # the two-chains-per-CU instance (bb_set_tuning key 21) where it applies: K >= 2 CUs
         big = [k for k in (2 * cus, 4 * cus) if k <= args.max_chains]
-        if big and not args.tuning and bb.set_tuning(21, -1) >= 0:
+        if big and not me.tri and not args.tuning and bb.set_tuning(21, -1) >= 0:
             bb.set_tuning(21, 1)
             try:
-                rec["chains_two_per_cu"] = bench_design(bb, name, X, y, cus, args, big)["chains"]
+                rec["chains_two_per_cu"] = bench_design(me, name, X, y, cus, args, big)["chains"]
             finally:
                 bb.set_tuning(21, 0)
         rec["source_sha"] = bb._build.source_sha()
-        path = os.path.join(args.out_dir, f"chains_{name}{args.tag}.json")
+        stem = "chains_tri_" if me.tri else "chains_"
+        path = os.path.join(args.out_dir, f"{stem}{name}{args.tag}.json")
         with open(path, "w") as f:
             json.dump(rec, f, indent=1)
             f.write("\n")
@@ -205,6 +253,11 @@ def main():
                   f"[{r['aggregate_sweeps_per_s']['min']:.0f}, "
                   f"{r['aggregate_sweeps_per_s']['max']:.0f}]  kernel "
                   f"{r['kernel_aggregate_sweeps_per_s']['median']:.0f}  "
+                  f"resident/CU {r['resident_per_cu']}", flush=True)
+        for r in rec.get("instances", []):
+            k = r["kernel_aggregate_sweeps_per_s"]
+            print(f"{name} instance {r['threads']:3d} threads K={r['chains']:5d} kernel "
+                  f"{k['median']:.0f} [{k['min']:.0f}, {k['max']:.0f}]  "
                   f"resident/CU {r['resident_per_cu']}", flush=True)
         print(f"{name} single call {rec['single_call_sweeps_per_s']} kernel "
               f"{rec['single_kernel_sweeps_per_s']}", flush=True)

@@ -1,94 +1,44 @@
 // bb_engine.cpp -- host side of the MI355X BayesBridge drop-in: the Gibbs driver
 // (restating Code/C/BridgeWrapper.cpp:207-313 and :434-537) over the HIP kernels of
-// bb_kernels.hip, RCCL for column-sharded multi-GPU runs, and the extern "C" entry
-// points declared in include/bayesbridge.h.
+// bb_kernels.hip, the chain batch, RCCL for column-sharded multi-GPU runs, and the engine,
+// chain-batch, group and .C sampler entry points declared in include/bayesbridge.h.  The
+// kernel-level entry points and the EM solver are in bb_prims.cpp; bb_host.h holds what the
+// two share.
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <chrono>
 #include <cxxabi.h>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
-#include <stdexcept>
-#include <string>
 #include <thread>
-#include <vector>
 
 #include "../../include/bayesbridge.h"
-#include "bb_kernels.h"
+#include "bb_host.h"
 #include "bb_ozaki.h"
-#include "bb_sparse.h"
 
 using namespace bb;
 
-namespace {
+namespace bb {
 
 thread_local std::string g_last_error;
+int g_device = 0;
+int g_verbose = 1;
+
+}  // namespace bb
+
+namespace {
+
 std::mutex g_mu;
 uint64_t g_seed = 0xB4E5B41D6EULL;
 uint64_t g_stream = 0;
-int g_device = 0;
-int g_verbose = 1;
 int g_use_r_rng = 1;
 // bb_debug_fail_member: member `g_debug_fail_member` of the next RCCL group run throws
 // before its sweep `g_debug_fail_sweep` (test hook for the group's failure handling)
 std::atomic<int> g_debug_fail_member{-1}, g_debug_fail_sweep{-1};
-
-void set_error(const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
-
-struct HipError : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-
-#define HIPCHECK(x)                                                                       \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            char b_[512];                                                                 \
-            snprintf(b_, sizeof(b_), "HIP error %s at %s:%d: %s", hipGetErrorName(e_),    \
-                     __FILE__, __LINE__, #x);                                             \
-            throw HipError(b_);                                                           \
-        }                                                                                 \
-    } while (0)
-
-#define NCCLCHECK(x)                                                                      \
-    do {                                                                                  \
-        ncclResult_t r_ = (x);                                                            \
-        if (r_ != ncclSuccess) {                                                          \
-            char b_[512];                                                                 \
-            snprintf(b_, sizeof(b_), "RCCL error %s at %s:%d", ncclGetErrorString(r_),    \
-                     __FILE__, __LINE__);                                                 \
-            throw HipError(b_);                                                           \
-        }                                                                                 \
-    } while (0)
-
-inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
-
-template <typename T>
-T *dalloc(size_t count, std::vector<void *> &owned) {
-    void *p = nullptr;
-    if (count == 0) count = 1;
-    HIPCHECK(hipMalloc(&p, count * sizeof(T)));
-    HIPCHECK(hipMemset(p, 0, count * sizeof(T)));
-    // the engine's streams are non-blocking: the zero fill must land before their first use
-    HIPCHECK(hipDeviceSynchronize());
-    owned.push_back(p);
-    return (T *)p;
-}
 
 // R's RNG, resolved at run time when this library is loaded inside R.
 struct RRng {
@@ -107,9 +57,9 @@ struct RRng {
     }
 } g_rrng;
 
-// Key for one .C call: from R's RNG if present, else (seed, stream++).  A call that runs
-// `count` chains takes the streams k1 .. k1 + count - 1 (one seed drawn under R's RNG).
-void next_call_key(uint64_t *k0, uint64_t *k1, int count = 1) {
+}  // namespace
+
+void bb::next_call_key(uint64_t *k0, uint64_t *k1, int count) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_use_r_rng && g_rrng.ok()) {
         g_rrng.get();
@@ -125,142 +75,6 @@ void next_call_key(uint64_t *k0, uint64_t *k1, int count = 1) {
     *k1 = g_stream;
     g_stream += (uint64_t)count;
 }
-
-// ---------------------------------------------------------------------------
-// Sparse design (CSC input): CSC + CSR copies on the device and the Gram pair list
-// (bb_sparse.h).  Built once at setup; X is constant over a chain.
-// ---------------------------------------------------------------------------
-// The canonical dgCMatrix form every CSC entry point requires (colptr[0] = 0,
-// non-decreasing, rows in [0, n), strictly increasing within a column); throws otherwise.
-// Both .C CSC paths (sparse engine and densified dense path) run it, so a malformed matrix
-// is refused the same way whichever path its shape selects.
-static void csc_validate(int n, int p, const int *cp, const int *ri) {
-    if (cp[0] != 0) throw HipError("CSC: colptr[0] must be 0");
-    for (int j = 0; j < p; ++j) {
-        if (cp[j + 1] < cp[j]) throw HipError("CSC: colptr must be non-decreasing");
-        for (int q = cp[j]; q < cp[j + 1]; ++q) {
-            if (ri[q] < 0 || ri[q] >= n) throw HipError("CSC: row index out of range");
-            if (q > cp[j] && ri[q] <= ri[q - 1])
-                throw HipError("CSC: row indices must be strictly increasing within a "
-                               "column (canonical dgCMatrix form)");
-        }
-    }
-}
-
-struct SparseDesign {
-    int n = 0, n_pad = 0, p = 0;
-    long nnz = 0;
-    size_t pairs = 0;
-    int *colptr = nullptr, *rowidx = nullptr, *rowptr = nullptr, *colidx = nullptr,
-        *cpos = nullptr, *pj = nullptr;
-    double *cval = nullptr, *rval = nullptr, *prod = nullptr;
-    unsigned *estart = nullptr;
-    unsigned short *pidx = nullptr;
-    int max_row = 0;        // largest row nnz
-    bool col_mode = false;  // by-column Gram kernel (max_row <= kSpColMaxRow)
-
-    // Validates the CSC (colptr[0] = 0, non-decreasing, rows in [0, n), strictly increasing
-    // within a column -- R's dgCMatrix is in this canonical form), transposes it on the host
-    // into a CSR with each entry's CSC position, uploads both and builds the pair list.
-    void build(hipStream_t s, int n_, int n_pad_, int p_, const int *cp, const int *ri,
-               const double *cv, std::vector<void *> &owned) {
-        n = n_;
-        n_pad = n_pad_;
-        p = p_;
-        csc_validate(n, p, cp, ri);
-        nnz = cp[p];
-        std::vector<int> rp(n_pad + 1, 0), ci(nnz > 0 ? nnz : 1), pos(nnz > 0 ? nnz : 1);
-        std::vector<double> rv(nnz > 0 ? nnz : 1);
-        for (long q = 0; q < nnz; ++q) ++rp[ri[q] + 1];
-        max_row = 0;
-        for (int r = 0; r < n_pad; ++r) max_row = std::max(max_row, rp[r + 1]);
-        col_mode = max_row <= kSpColMaxRow;
-        for (int r = 0; r < n_pad; ++r) rp[r + 1] += rp[r];
-        std::vector<int> next(rp.begin(), rp.end() - 1);
-        for (int j = 0; j < p; ++j)
-            for (int q = cp[j]; q < cp[j + 1]; ++q) {
-                const int k = next[ri[q]]++;
-                ci[k] = j;
-                rv[k] = cv[q];
-                pos[k] = q;
-            }
-        colptr = dalloc<int>(p + 1, owned);
-        rowidx = dalloc<int>(nnz, owned);
-        cval = dalloc<double>(nnz, owned);
-        rowptr = dalloc<int>(n_pad + 1, owned);
-        colidx = dalloc<int>(nnz, owned);
-        rval = dalloc<double>(nnz, owned);
-        cpos = dalloc<int>(nnz, owned);
-        HIPCHECK(hipMemcpy(colptr, cp, (size_t)(p + 1) * sizeof(int), hipMemcpyHostToDevice));
-        if (nnz > 0) {
-            HIPCHECK(hipMemcpy(rowidx, ri, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(cval, cv, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(colidx, ci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(rval, rv.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(cpos, pos.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-        }
-        HIPCHECK(hipMemcpy(rowptr, rp.data(), (size_t)(n_pad + 1) * sizeof(int),
-                           hipMemcpyHostToDevice));
-        // pair counts per output column, host scan, then the pair list itself
-        unsigned long long *dcnt = nullptr, *dbase = nullptr;
-        HIPCHECK(hipMalloc(&dcnt, (size_t)n_pad * sizeof(unsigned long long)));
-        launch_sp_count(s, rowptr, colidx, cpos, colptr, n_pad, dcnt);
-        std::vector<unsigned long long> cnt(n_pad), base(n_pad);
-        HIPCHECK(hipMemcpyAsync(cnt.data(), dcnt, cnt.size() * sizeof(unsigned long long),
-                                hipMemcpyDeviceToHost, s));
-        HIPCHECK(hipStreamSynchronize(s));
-        (void)hipFree(dcnt);
-        unsigned long long tot = 0;
-        for (int c = 0; c < n_pad; ++c) {
-            base[c] = tot;
-            tot += cnt[c];
-        }
-        if (tot > 0xFFFFFF00ull)
-            throw HipError("sparse Gram: more than 2^32 - 1 column pairs (X too dense for the "
-                           "pair-list Gram; use the dense entry point)");
-        pairs = (size_t)tot;
-        size_t fr = 0, total_mem = 0;
-        HIPCHECK(hipMemGetInfo(&fr, &total_mem));
-        const size_t need = pairs * (sizeof(double) + (col_mode ? 2 : sizeof(int))) +
-                            (tri_count(n_pad) + 1) * sizeof(unsigned);
-        if (need + (size_t(1) << 28) > fr) {
-            char b[256];
-            snprintf(b, sizeof(b), "sparse Gram: pair list needs %.2f GB, %.2f GB free", need / 1e9,
-                     fr / 1e9);
-            throw HipError(b);
-        }
-        estart = dalloc<unsigned>(tri_count(n_pad) + 1, owned);
-        prod = dalloc<double>(pairs, owned);
-        if (col_mode)
-            pidx = dalloc<unsigned short>(pairs, owned);
-        else
-            pj = dalloc<int>(pairs, owned);
-        HIPCHECK(hipMalloc(&dbase, (size_t)n_pad * sizeof(unsigned long long)));
-        HIPCHECK(hipMemcpyAsync(dbase, base.data(), base.size() * sizeof(unsigned long long),
-                                hipMemcpyHostToDevice, s));
-        launch_sp_build(s, rowptr, colidx, cpos, rval, colptr, rowidx, cval, n_pad, dbase, estart,
-                        prod, pj, pidx);
-        const unsigned last = (unsigned)tot;
-        HIPCHECK(hipMemcpyAsync(estart + tri_count(n_pad), &last, sizeof(unsigned),
-                                hipMemcpyHostToDevice, s));
-        HIPCHECK(hipStreamSynchronize(s));
-        (void)hipFree(dbase);
-    }
-
-    // tri (packed upper triangle of X diag(D) X', n_pad wide) and xu = X u
-    void gram(hipStream_t s, const double *D, const double *u, double *tri, double *xu,
-              const int *gate = nullptr) const {
-        if (col_mode) {
-            launch_sp_gram_col(s, rowptr, colidx, rval, estart, prod, pidx, D, u, n_pad, max_row,
-                               tri, xu, gate);
-        } else {
-            launch_sp_gram(s, estart, prod, pj, D, n_pad, tri, gate);
-            launch_sp_rows(s, rowptr, colidx, rval, n_pad, u, D, xu, tri, gate);
-        }
-    }
-};
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // Engine
@@ -1627,6 +1441,61 @@ void ring_copy(double *dst, const double *src, size_t count) {
     HIPCHECK(hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost));
 }
 
+// f(k, slot, run) for each contiguous run of the slots [slot0, slot0 + count) in a ring of
+// `cap`: slots slot .. slot + run - 1 hold the samples k .. k + run - 1 of the request
+template <class F>
+void ring_runs(int slot0, int count, int cap, F f) {
+    for (int k = 0; k < count;) {
+        const int slot = (slot0 + k) % cap;
+        const int run = std::min(count - k, cap - slot);
+        f(k, slot, run);
+        k += run;
+    }
+}
+
+// Ring slots [slot0, slot0 + count) of some traces to the host: each is `w` doubles per slot
+// from `ring` (slot 0 of the ring) to `dst`, skipped when dst is null.
+struct RingTrace {
+    double *dst;
+    const double *ring;
+    size_t w;
+};
+void ring_fetch(int slot0, int count, int cap, std::initializer_list<RingTrace> traces) {
+    ring_runs(slot0, count, cap, [&](int k, int slot, int run) {
+        for (const RingTrace &t : traces)
+            if (t.dst) ring_copy(t.dst + k * t.w, t.ring + slot * t.w, run * t.w);
+    });
+}
+
+// (tau, sig2, alpha) of a DevScalars on the device; the write keeps its other fields
+void scalars_read(const DevScalars *dev, double *tau, double *sig2, double *alpha) {
+    DevScalars s;
+    HIPCHECK(hipMemcpy(&s, dev, sizeof(s), hipMemcpyDeviceToHost));
+    if (tau) *tau = s.tau;
+    if (sig2) *sig2 = s.sig2;
+    if (alpha) *alpha = s.alpha;
+}
+void scalars_write(DevScalars *dev, double tau, double sig2, double alpha) {
+    DevScalars s;
+    HIPCHECK(hipMemcpy(&s, dev, sizeof(s), hipMemcpyDeviceToHost));
+    s.tau = tau;
+    s.sig2 = sig2;
+    s.alpha = alpha;
+    HIPCHECK(hipMemcpy(dev, &s, sizeof(s), hipMemcpyHostToDevice));
+}
+
+// The output traces of a .C sampler call: P x M (M) column-major, or P x M x K (M x K) for K
+// chains.  `lam` is lambda, or omega for the triangle mixture, whose u and shape are optional.
+struct Traces {
+    double *beta, *lam, *sig2, *tau, *alpha, *u = nullptr, *shape = nullptr;
+    // chain k's P x M (M) slice of K chains' outputs
+    Traces chain(size_t k, size_t p, size_t m) const {
+        auto at = [&](double *q, size_t w) { return q ? q + k * w * m : nullptr; };
+        return {at(beta, p), at(lam, p), at(sig2, 1), at(tau, 1), at(alpha, 1), at(u, p),
+                at(shape, p)};
+    }
+};
+
 // Enqueue throttle of the .C drivers: mark() records the work enqueued so far on a stream and
 // waits until at most two marked blocks are ahead of the device.
 struct Throttle {
@@ -1760,8 +1629,7 @@ struct bb_chains {
 
     // Trace slots [slot0, slot0 + count) of EVERY chain -> samples [s0, s0 + count) of the
     // P x M x K (M x K) outputs: one strided copy per contiguous run of the ring and trace.
-    void copy_out(int slot0, int count, int s0, int m, double *obeta, double *olam, double *osig2,
-                  double *otau, double *oalpha, double *ou = nullptr, double *oshape = nullptr) {
+    void copy_out(int slot0, int count, int s0, int m, const Traces &o) {
         auto strided = [&](double *dst, const double *src, size_t w, int k, int sl, int run) {
             if (!dst) return;
             if (K == 1 || (run == cap && run == m)) {  // one contiguous block (no ring wrap)
@@ -1774,18 +1642,15 @@ struct bb_chains {
                                  (size_t)run * w * sizeof(double), (size_t)K,
                                  hipMemcpyDeviceToHost));
         };
-        for (int k = 0; k < count;) {
-            const int sl = (slot0 + k) % cap;
-            const int run = std::min(count - k, cap - sl);
-            strided(obeta, tr_beta, (size_t)p, k, sl, run);
-            strided(olam, tr_lam, (size_t)p, k, sl, run);
-            strided(osig2, tr_sig2, 1, k, sl, run);
-            strided(otau, tr_tau, 1, k, sl, run);
-            strided(oalpha, tr_alpha, 1, k, sl, run);
-            strided(ou, tr_u, (size_t)p, k, sl, run);
-            strided(oshape, tr_shape, (size_t)p, k, sl, run);
-            k += run;
-        }
+        ring_runs(slot0, count, cap, [&](int k, int sl, int run) {
+            strided(o.beta, tr_beta, (size_t)p, k, sl, run);
+            strided(o.lam, tr_lam, (size_t)p, k, sl, run);
+            strided(o.sig2, tr_sig2, 1, k, sl, run);
+            strided(o.tau, tr_tau, 1, k, sl, run);
+            strided(o.alpha, tr_alpha, 1, k, sl, run);
+            strided(o.u, tr_u, (size_t)p, k, sl, run);
+            strided(o.shape, tr_shape, (size_t)p, k, sl, run);
+        });
     }
 
     uint64_t base_stream = 0;
@@ -1861,43 +1726,34 @@ void bb_config_default(bb_config *c) {
     c->gram_mode = 1;
 }
 
-int bb_engine_create(const bb_config *cfg, const double *X_local, const double *y,
-                     bb_engine **out) {
+// the engine of a dense (X_local) or sparse (spin) design
+static int engine_create(const bb_config *cfg, const double *X_local, const double *y,
+                         const SparseIn *spin, bb_engine **out) {
     *out = nullptr;
     bb_engine *e = new bb_engine();
-    try {
+    const int rc = guarded([&] {
         e->cfg = *cfg;
         if (e->cfg.p_local <= 0) e->cfg.p_local = e->cfg.p;
         if (e->cfg.world < 1) e->cfg.world = 1;
         if (cfg->n <= 0 || cfg->p <= 0) throw HipError("n and p must be positive");
-        engine_setup(e, X_local, y, nullptr);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
+        engine_setup(e, X_local, y, spin);
+    });
+    if (rc == 0)
+        *out = e;
+    else
         delete e;
-        return -1;
-    }
-    *out = e;
-    return 0;
+    return rc;
+}
+
+int bb_engine_create(const bb_config *cfg, const double *X_local, const double *y,
+                     bb_engine **out) {
+    return engine_create(cfg, X_local, y, nullptr, out);
 }
 
 int bb_engine_create_csc(const bb_config *cfg, const int *colptr, const int *rowidx,
                          const double *val, const double *y, bb_engine **out) {
-    *out = nullptr;
-    bb_engine *e = new bb_engine();
-    try {
-        e->cfg = *cfg;
-        if (e->cfg.p_local <= 0) e->cfg.p_local = e->cfg.p;
-        if (e->cfg.world < 1) e->cfg.world = 1;
-        if (cfg->n <= 0 || cfg->p <= 0) throw HipError("n and p must be positive");
-        SparseIn sp{colptr, rowidx, val};
-        engine_setup(e, nullptr, y, &sp);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        delete e;
-        return -1;
-    }
-    *out = e;
-    return 0;
+    const SparseIn sp{colptr, rowidx, val};
+    return engine_create(cfg, nullptr, y, &sp, out);
 }
 
 long long bb_engine_sparse_pairs(const bb_engine *e) {
@@ -1953,79 +1809,44 @@ static void agree_kmax_ranks(bb_engine *e) {
 }
 
 int bb_engine_comm_init(bb_engine *e, const void *id_bytes) {
-    try {
-        HIPCHECK(hipSetDevice(e->cfg.device));
+    return guarded(e->cfg.device, [&] {
         ncclUniqueId id;
         memcpy(&id, id_bytes, sizeof(id));
         NCCLCHECK(ncclCommInitRank(&e->comm, e->cfg.world, id, e->cfg.rank));
         agree_kmax_ranks(e);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_init_state(bb_engine *e) {
-    try {
-        HIPCHECK(hipSetDevice(e->cfg.device));
-        engine_init_state(e);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    return guarded(e->cfg.device, [&] { engine_init_state(e); });
 }
 
 int bb_engine_run(bb_engine *e, uint64_t t0, int count, int first_slot, int slot_step,
                   int mcmc_phase) {
-    try {
-        HIPCHECK(hipSetDevice(e->cfg.device));
+    return guarded(e->cfg.device, [&] {
         e->run(t0, count, first_slot, slot_step, mcmc_phase);
         HIPCHECK(hipGetLastError());
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_sync(bb_engine *e) {
-    try {
-        HIPCHECK(hipStreamSynchronize(e->stream));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    return guarded([&] { HIPCHECK(hipStreamSynchronize(e->stream)); });
 }
 
 int bb_engine_get_trace(bb_engine *e, int slot0, int count, double *beta, double *lambda,
                         double *sig2, double *tau, double *alpha) {
-    try {
+    return guarded([&] {
         HIPCHECK(hipStreamSynchronize(e->stream));
         const size_t pl = (size_t)e->p_loc;
-        // slots [slot0, slot0 + count) of the ring: at most two contiguous runs per trace
-        for (int k = 0; k < count;) {
-            const int s = (slot0 + k) % e->cap;
-            const int run = std::min(count - k, e->cap - s);
-            if (beta) ring_copy(beta + k * pl, e->tr_beta + s * pl, run * pl);
-            if (lambda) ring_copy(lambda + k * pl, e->tr_lam + s * pl, run * pl);
-            if (sig2) ring_copy(sig2 + k, e->tr_sig2 + s, run);
-            if (tau) ring_copy(tau + k, e->tr_tau + s, run);
-            if (alpha) ring_copy(alpha + k, e->tr_alpha + s, run);
-            k += run;
-        }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        ring_fetch(slot0, count, e->cap,
+                   {{beta, e->tr_beta, pl}, {lambda, e->tr_lam, pl}, {sig2, e->tr_sig2, 1},
+                    {tau, e->tr_tau, 1}, {alpha, e->tr_alpha, 1}});
+    });
 }
 
 int bb_engine_get_state(bb_engine *e, double *beta, double *lambda, double *tau, double *sig2,
                         double *alpha) {
-    try {
+    return guarded([&] {
         HIPCHECK(hipStreamSynchronize(e->stream));
         if (beta)
             HIPCHECK(hipMemcpy(beta, e->beta, (size_t)e->p_loc * sizeof(double),
@@ -2033,82 +1854,47 @@ int bb_engine_get_state(bb_engine *e, double *beta, double *lambda, double *tau,
         if (lambda)
             HIPCHECK(hipMemcpy(lambda, e->lam, (size_t)e->p_loc * sizeof(double),
                                hipMemcpyDeviceToHost));
-        DevScalars s;
-        HIPCHECK(hipMemcpy(&s, e->sc, sizeof(s), hipMemcpyDeviceToHost));
-        if (tau) *tau = s.tau;
-        if (sig2) *sig2 = s.sig2;
-        if (alpha) *alpha = s.alpha;
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        scalars_read(e->sc, tau, sig2, alpha);
+    });
 }
 
 int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig2,
                         double alpha) {
-    try {
+    return guarded([&] {
         HIPCHECK(hipStreamSynchronize(e->stream));
         HIPCHECK(hipMemcpy(e->beta, beta, (size_t)e->p_loc * sizeof(double),
                            hipMemcpyHostToDevice));
-        DevScalars s;
-        HIPCHECK(hipMemcpy(&s, e->sc, sizeof(s), hipMemcpyDeviceToHost));
-        s.tau = tau;
-        s.sig2 = sig2;
-        s.alpha = alpha;
-        HIPCHECK(hipMemcpy(e->sc, &s, sizeof(s), hipMemcpyHostToDevice));
+        scalars_write(e->sc, tau, sig2, alpha);
         e->xbeta();
         HIPCHECK(hipStreamSynchronize(e->stream));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_method(const bb_engine *e) { return e->method; }
 
 int bb_engine_get_omega(bb_engine *e, double *omega) {
-    try {
+    return guarded([&] {
         if (e->method != 6) throw HipError("not a logistic engine");
         HIPCHECK(hipStreamSynchronize(e->stream));
         HIPCHECK(hipMemcpy(omega, e->omega, (size_t)e->n * sizeof(double), hipMemcpyDeviceToHost));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_get_tri_trace(bb_engine *e, int slot0, int count, double *u, double *shape) {
-    try {
+    return guarded([&] {
         if (e->method != 4) throw HipError("not a triangle-method engine");
         HIPCHECK(hipStreamSynchronize(e->stream));
         const size_t pl = (size_t)e->p_loc;
-        for (int k = 0; k < count;) {
-            const int s = (slot0 + k) % e->cap;
-            const int run = std::min(count - k, e->cap - s);
-            if (u) ring_copy(u + k * pl, e->tr_u + s * pl, run * pl);
-            if (shape) ring_copy(shape + k * pl, e->tr_shape + s * pl, run * pl);
-            k += run;
-        }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        ring_fetch(slot0, count, e->cap, {{u, e->tr_u, pl}, {shape, e->tr_shape, pl}});
+    });
 }
 
 int bb_engine_set_tri_state(bb_engine *e, const double *u) {
-    try {
+    return guarded([&] {
         if (e->method != 4) throw HipError("not a triangle-method engine");
         HIPCHECK(hipStreamSynchronize(e->stream));
         HIPCHECK(hipMemcpy(e->u, u, (size_t)e->p_loc * sizeof(double), hipMemcpyHostToDevice));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_get_tri_basis(bb_engine *e, double *tV, double *a, double *d) {
@@ -2155,7 +1941,7 @@ int bb_engine_reset_timing(bb_engine *e) {
 }
 
 int bb_engine_phase_times(bb_engine *e, double *ms, int cap, int *samples) {
-    try {
+    return guarded([&] {
         HIPCHECK(hipStreamSynchronize(e->stream));
         std::vector<double> acc(PH_COUNT, 0.0);
         for (auto &marks : e->sweep_marks)
@@ -2168,11 +1954,7 @@ int bb_engine_phase_times(bb_engine *e, double *ms, int cap, int *samples) {
         const double ns = e->sweep_marks.empty() ? 1.0 : (double)e->sweep_marks.size();
         for (int i = 0; i < cap && i < PH_COUNT; ++i) ms[i] = acc[i] / ns;
         if (samples) *samples = (int)e->sweep_marks.size();
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 const char *bb_phase_name(int i) { return (i >= 0 && i < PH_COUNT) ? kPhaseNames[i] : ""; }
@@ -2180,7 +1962,7 @@ int bb_phase_count(void) { return PH_COUNT; }
 
 int bb_engine_kernel_times(bb_engine *e, double *gram_ms_avg, double *sweep_ms_avg,
                            int *samples) {
-    try {
+    return guarded([&] {
         HIPCHECK(hipStreamSynchronize(e->stream));
         double g = 0, s = 0;
         int ng = 0, ns = 0;
@@ -2204,11 +1986,7 @@ int bb_engine_kernel_times(bb_engine *e, double *gram_ms_avg, double *sweep_ms_a
         if (gram_ms_avg) *gram_ms_avg = ng ? g / ng : 0.0;
         if (sweep_ms_avg) *sweep_ms_avg = ns ? s / ns : 0.0;
         if (samples) *samples = ns;
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_timed_brackets(bb_engine *e, int *count) {
@@ -2222,7 +2000,7 @@ int bb_engine_timed_brackets(bb_engine *e, int *count) {
 
 int bb_engine_nid_mixed(bb_engine *e, unsigned long long *mixed_sweeps,
                         unsigned long long *products32, double *eta, int *k2, int *holds_x32) {
-    try {
+    return guarded([&] {
         NidState h{};
         if (e->nid) {
             HIPCHECK(hipMemcpyAsync(&h, e->nid, sizeof(h), hipMemcpyDeviceToHost, e->stream));
@@ -2233,11 +2011,7 @@ int bb_engine_nid_mixed(bb_engine *e, unsigned long long *mixed_sweeps,
         if (eta) *eta = h.eta;
         if (k2) *k2 = h.k2;
         if (holds_x32) *holds_x32 = e->X32 != nullptr;
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_engine_nid_bound(bb_engine *e, double *lambda_x, int *kmax) {
@@ -2249,7 +2023,7 @@ int bb_engine_nid_bound(bb_engine *e, double *lambda_x, int *kmax) {
 int bb_engine_nid_stats(bb_engine *e, unsigned long long *cheb_sweeps,
                         unsigned long long *products, unsigned long long *chol_sweeps,
                         double *eps, int *mode) {
-    try {
+    return guarded([&] {
         NidState h{};
         if (e->nid) {
             HIPCHECK(hipMemcpyAsync(&h, e->nid, sizeof(h), hipMemcpyDeviceToHost, e->stream));
@@ -2260,11 +2034,7 @@ int bb_engine_nid_stats(bb_engine *e, unsigned long long *cheb_sweeps,
         if (chol_sweeps) *chol_sweeps = h.n_chol;
         if (eps) *eps = e->nid ? h.eps : -1.0;
         if (mode) *mode = e->nid ? h.mode : -1;
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_kernel_instance(const char *phase, char *buf, int len) {
@@ -2307,13 +2077,7 @@ int bb_engine_launch_counts(bb_engine *e, unsigned long long *lambda_xu,
 }
 
 int bb_engine_error_flags(bb_engine *e, uint32_t *flags) {
-    try {
-        *flags = e->read_err();
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    return guarded([&] { *flags = e->read_err(); });
 }
 
 // ---------------------------------------------------------------------------
@@ -2398,67 +2162,39 @@ int bb_chains_set_threads(bb_chains *b, int threads) {
 }
 
 int bb_chains_init_state(bb_chains *b) {
-    try {
-        HIPCHECK(hipSetDevice(b->proto->cfg.device));
-        b->init_state();
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    return guarded(b->proto->cfg.device, [&] { b->init_state(); });
 }
 
 int bb_chains_run(bb_chains *b, uint64_t t0, int count, int first_slot, int slot_step,
                   int mcmc_phase) {
     (void)mcmc_phase;  // selects the prior of the alpha MH step: alpha is known here
-    try {
-        HIPCHECK(hipSetDevice(b->proto->cfg.device));
+    return guarded(b->proto->cfg.device, [&] {
         b->run(t0, count, first_slot, slot_step);
         HIPCHECK(hipGetLastError());
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_chains_sync(bb_chains *b) {
-    try {
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    return guarded([&] { HIPCHECK(hipStreamSynchronize(b->stream())); });
 }
 
 int bb_chains_get_trace(bb_chains *b, int chain, int slot0, int count, double *beta,
                         double *lambda, double *sig2, double *tau, double *alpha) {
-    try {
+    return guarded([&] {
         b->check_chain(chain);
         if (slot0 < 0 || count < 0) throw HipError("bb_chains_get_trace: slot0 and count must be >= 0");
         HIPCHECK(hipStreamSynchronize(b->stream()));
         const size_t pl = (size_t)b->p, ring = (size_t)chain * b->cap;
-        for (int k = 0; k < count;) {
-            const int s = (slot0 + k) % b->cap;
-            const int run = std::min(count - k, b->cap - s);
-            if (beta) ring_copy(beta + k * pl, b->tr_beta + (ring + s) * pl, run * pl);
-            if (lambda) ring_copy(lambda + k * pl, b->tr_lam + (ring + s) * pl, run * pl);
-            if (sig2) ring_copy(sig2 + k, b->tr_sig2 + ring + s, run);
-            if (tau) ring_copy(tau + k, b->tr_tau + ring + s, run);
-            if (alpha) ring_copy(alpha + k, b->tr_alpha + ring + s, run);
-            k += run;
-        }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        ring_fetch(slot0, count, b->cap,
+                   {{beta, b->tr_beta + ring * pl, pl}, {lambda, b->tr_lam + ring * pl, pl},
+                    {sig2, b->tr_sig2 + ring, 1}, {tau, b->tr_tau + ring, 1},
+                    {alpha, b->tr_alpha + ring, 1}});
+    });
 }
 
 int bb_chains_get_state(bb_chains *b, int chain, double *beta, double *lambda, double *tau,
                         double *sig2, double *alpha) {
-    try {
+    return guarded([&] {
         b->check_chain(chain);
         HIPCHECK(hipStreamSynchronize(b->stream()));
         const size_t pl = (size_t)b->p;
@@ -2468,74 +2204,44 @@ int bb_chains_get_state(bb_chains *b, int chain, double *beta, double *lambda, d
         if (lambda)
             HIPCHECK(hipMemcpy(lambda, b->lam + chain * pl, pl * sizeof(double),
                                hipMemcpyDeviceToHost));
-        DevScalars s;
-        HIPCHECK(hipMemcpy(&s, b->sc + chain, sizeof(s), hipMemcpyDeviceToHost));
-        if (tau) *tau = s.tau;
-        if (sig2) *sig2 = s.sig2;
-        if (alpha) *alpha = s.alpha;
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        scalars_read(b->sc + chain, tau, sig2, alpha);
+    });
 }
 
 int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau, double sig2,
                         double alpha) {
-    try {
+    return guarded([&] {
         b->check_chain(chain);
         HIPCHECK(hipStreamSynchronize(b->stream()));
         const size_t pl = (size_t)b->p;
         HIPCHECK(hipMemcpy(b->beta + chain * pl, beta, pl * sizeof(double),
                            hipMemcpyHostToDevice));
-        DevScalars s;
-        HIPCHECK(hipMemcpy(&s, b->sc + chain, sizeof(s), hipMemcpyDeviceToHost));
-        s.tau = tau;
-        s.sig2 = sig2;
-        s.alpha = alpha;
-        HIPCHECK(hipMemcpy(b->sc + chain, &s, sizeof(s), hipMemcpyHostToDevice));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        scalars_write(b->sc + chain, tau, sig2, alpha);
+    });
 }
 
 int bb_chains_get_tri_trace(bb_chains *b, int chain, int slot0, int count, double *u,
                             double *shape) {
-    try {
+    return guarded([&] {
         b->check_chain(chain);
         if (!b->tri()) throw HipError("not a triangle-method chain batch");
         if (slot0 < 0 || count < 0)
             throw HipError("bb_chains_get_tri_trace: slot0 and count must be >= 0");
         HIPCHECK(hipStreamSynchronize(b->stream()));
         const size_t pl = (size_t)b->p, ring = (size_t)chain * b->cap;
-        for (int k = 0; k < count;) {
-            const int s = (slot0 + k) % b->cap;
-            const int run = std::min(count - k, b->cap - s);
-            if (u) ring_copy(u + k * pl, b->tr_u + (ring + s) * pl, run * pl);
-            if (shape) ring_copy(shape + k * pl, b->tr_shape + (ring + s) * pl, run * pl);
-            k += run;
-        }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+        ring_fetch(slot0, count, b->cap,
+                   {{u, b->tr_u + ring * pl, pl}, {shape, b->tr_shape + ring * pl, pl}});
+    });
 }
 
 int bb_chains_set_tri_state(bb_chains *b, int chain, const double *u) {
-    try {
+    return guarded([&] {
         b->check_chain(chain);
         if (!b->tri()) throw HipError("not a triangle-method chain batch");
         HIPCHECK(hipStreamSynchronize(b->stream()));
         HIPCHECK(hipMemcpy(b->u + (size_t)chain * b->p, u, (size_t)b->p * sizeof(double),
                            hipMemcpyHostToDevice));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d) {
@@ -2764,7 +2470,7 @@ int bb_group_run(bb_group *g, uint64_t t0, int count, int first_slot, int slot_s
             }
         return 0;
     }
-    try {
+    return guarded([&] {
         for (int k = 0; k < count; ++k) {
             const uint64_t t = t0 + (uint64_t)k;
             const int slot = first_slot < 0 ? -1 : first_slot + k * slot_step;
@@ -2849,11 +2555,7 @@ int bb_group_run(bb_group *g, uint64_t t0, int count, int first_slot, int slot_s
             }
         }
         HIPCHECK(hipGetLastError());
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_group_sync(bb_group *g) {
@@ -2861,21 +2563,17 @@ int bb_group_sync(bb_group *g) {
         set_error("shard group unusable: a member failed and its communicators were aborted");
         return -1;
     }
-    try {
+    return guarded([&] {
         for (auto *m : g->members) {
             g->on(m);
             HIPCHECK(hipStreamSynchronize(m->stream));
         }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 int bb_group_init_state(bb_group *g) {
     // p > n (Woodbury) start: beta = 0, then the pre-burn tau draw from the summed red1
-    try {
+    return guarded([&] {
         for (auto *m : g->members) {
             if (m->G != nullptr) throw HipError("group init supports the p > n path only");
             g->on(m);
@@ -2900,815 +2598,10 @@ int bb_group_init_state(bb_group *g) {
             g->on(m);
             HIPCHECK(hipStreamSynchronize(m->stream));
         }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        return -1;
-    }
-    return 0;
+    });
 }
 
 }  // extern "C"
-
-// ---------------------------------------------------------------------------
-// kernel-level entry points
-// ---------------------------------------------------------------------------
-int bb_retstable_batch(double *x, const double *alpha, const double *V0, const double *h, int num,
-                       uint64_t seed, uint64_t stream, uint64_t t, int group) {
-    if (num <= 0) return 0;
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        double *da = dalloc<double>(num, owned), *dv = dalloc<double>(num, owned),
-               *dh = dalloc<double>(num, owned), *dx = dalloc<double>(num, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        HIPCHECK(hipMemcpy(da, alpha, num * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dv, V0, num * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dh, h, num * sizeof(double), hipMemcpyHostToDevice));
-        if (group <= 0) group = stable_group_for(num);
-        launch_retstable_batch(0, dx, da, dv, dh, num, seed, stream, t, group, de);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpy(x, dx, num * sizeof(double), hipMemcpyDeviceToHost));
-        uint32_t f = 0;
-        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
-        if (f & 4u) {
-            fprintf(stderr, "Problem with parameter.\n");  // retstable.cpp:112-115
-        }
-        rc = (int)(f & ~4u) ? -2 : 0;
-        if (rc) set_error("retstable: rejection cap reached (flags %u)", f);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_pg_batch(double *omega, const double *psi, int n, uint64_t seed, uint64_t stream,
-                uint64_t t) {
-    if (n <= 0) return 0;
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        double *dp = dalloc<double>(n, owned), *dw = dalloc<double>(n, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        HIPCHECK(hipMemcpy(dp, psi, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        launch_pg(0, dp, n, n, seed, stream, t, dw, de);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpy(omega, dw, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        uint32_t f = 0;
-        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
-        if (f) {
-            set_error("pg: rejection cap reached (flags %u)", f);
-            rc = -2;
-        }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_trunc_batch(int mode, int num, double *x, const double *p0, const double *p1,
-                   const double *p2, const double *p3, uint64_t seed, uint64_t stream) {
-    if (num <= 0) return 0;
-    if (mode < 0 || mode > 5) {
-        set_error("bb_trunc_batch: invalid mode %d", mode);
-        return -1;
-    }
-    static const int nparams[6] = {3, 4, 4, 2, 3, 3};
-    const double *src[4] = {p0, p1, p2, p3};
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        double *dp[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int k = 0; k < nparams[mode]; ++k) {
-            dp[k] = dalloc<double>(num, owned);
-            HIPCHECK(hipMemcpy(dp[k], src[k], num * sizeof(double), hipMemcpyHostToDevice));
-        }
-        double *dx = dalloc<double>(num, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        launch_trunc_batch(0, mode, num, dx, dp[0], dp[1], dp[2], dp[3], seed, stream, de);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpy(x, dx, num * sizeof(double), hipMemcpyDeviceToHost));
-        uint32_t f = 0;
-        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
-        if (f & 256u) {  // BridgeWrapper.cpp:815-822
-            for (int i = 0; i < num; ++i)
-                if (std::isnan(p0[i]) || std::isnan(p1[i]) || std::isnan(p2[i]) ||
-                    std::isinf(p0[i]))
-                    fprintf(stderr, "rtexpon_rate: caught non finite left value: %g; x[i] = %g.\n",
-                            p0[i], (double)NAN);  // printed before the draw overwrites it
-        }
-        rc = (f & (64u | 128u)) ? -2 : 0;
-        if (rc) set_error("truncated draw: %s (flags %u)",
-                          (f & 128u) ? "empty truncation interval" : "rejection cap reached", f);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_rrtgamma_batch(int num, double *x, const double *shape, const double *rate,
-                      const double *right_t, uint64_t seed, uint64_t stream) {
-    if (num <= 0) return 0;
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const double *src[3] = {shape, rate, right_t};
-        double *dp[3];
-        for (int k = 0; k < 3; ++k) {
-            dp[k] = dalloc<double>(num, owned);
-            HIPCHECK(hipMemcpy(dp[k], src[k], num * sizeof(double), hipMemcpyHostToDevice));
-        }
-        double *dx = dalloc<double>(num, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        launch_rrtgamma_batch(0, num, dx, dp[0], dp[1], dp[2], seed, stream, de);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpy(x, dx, num * sizeof(double), hipMemcpyDeviceToHost));
-        uint32_t f = 0;
-        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
-        rc = f ? -2 : 0;
-        if (rc) set_error("rrtgamma: rejection cap reached (flags %u)", f);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_sample_lambda(double *lambda, const double *beta, int p, double alpha, double tau,
-                     uint64_t seed, uint64_t stream, uint64_t t, uint64_t j0, int group) {
-    if (p <= 0) return 0;
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        double *db = dalloc<double>(p, owned), *dl = dalloc<double>(p, owned);
-        DevScalars *dsc = dalloc<DevScalars>(1, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        DevScalars s{};
-        s.tau = tau;
-        s.alpha = alpha;
-        HIPCHECK(hipMemcpy(dsc, &s, sizeof(s), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(db, beta, p * sizeof(double), hipMemcpyHostToDevice));
-        if (group <= 0) group = stable_group_for(p);
-        launch_lambda(0, db, p, p, j0, dsc, seed, stream, t, LAMBDA_ONLY, group, dl, nullptr,
-                      nullptr, nullptr, de);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpy(lambda, dl, p * sizeof(double), hipMemcpyDeviceToHost));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_bench_lambda(const double *beta, int p, double alpha, double tau, int group,
-                    int noinline, int reps, double *ms_avg, double *lambda_out) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        double *db = dalloc<double>(p, owned), *dl = dalloc<double>(p, owned);
-        DevScalars *dsc = dalloc<DevScalars>(1, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        DevScalars s{};
-        s.tau = tau;
-        s.alpha = alpha;
-        HIPCHECK(hipMemcpy(dsc, &s, sizeof(s), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(db, beta, p * sizeof(double), hipMemcpyHostToDevice));
-        hipEvent_t e0, e1;
-        HIPCHECK(hipEventCreate(&e0));
-        HIPCHECK(hipEventCreate(&e1));
-        launch_lambda_variant(0, db, p, dsc, 1, 0, 1, group, noinline, dl, de);  // warm
-        HIPCHECK(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; ++r)
-            launch_lambda_variant(0, db, p, dsc, 1, 0, 2 + r, group, noinline, dl, de);
-        HIPCHECK(hipEventRecord(e1, 0));
-        HIPCHECK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-        *ms_avg = ms / reps;
-        if (lambda_out)
-            HIPCHECK(hipMemcpy(lambda_out, dl, p * sizeof(double), hipMemcpyDeviceToHost));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_bench_chol(int m, int reps, double *ms_factor, double *ms_solve,
-                  unsigned long long *trace) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int m_pad = round_up(m, kNB);
-        // SPD test matrix: I * m + small symmetric perturbation, built on the host once
-        std::vector<double> h((size_t)m_pad * (m_pad + kNB), 0.0);
-        for (int c = 0; c < m_pad; ++c)
-            for (int r = 0; r <= c; ++r)
-                h[(size_t)r + (size_t)c * m_pad] =
-                    (r == c) ? (double)m_pad : 0.5 * std::sin(0.37 * r + 0.11 * c);
-        for (int r = 0; r < m_pad; ++r) h[(size_t)r + (size_t)m_pad * m_pad] = 1.0;
-        double *src = dalloc<double>(h.size(), owned), *dA = dalloc<double>(h.size(), owned);
-        HIPCHECK(hipMemcpy(src, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-        double *Wd = dalloc<double>(chol_wd_words(m_pad), owned);
-        unsigned int *fl = dalloc<unsigned int>(chol_flag_words(m_pad, 1), owned);
-        double *W = dalloc<double>((size_t)m_pad, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        hipEvent_t e0, e1, e2;
-        HIPCHECK(hipEventCreate(&e0));
-        HIPCHECK(hipEventCreate(&e1));
-        HIPCHECK(hipEventCreate(&e2));
-        double tf = 0, ts = 0;
-        for (int it = 0; it <= reps; ++it) {
-            HIPCHECK(hipMemcpyAsync(dA, src, h.size() * sizeof(double), hipMemcpyDeviceToDevice, 0));
-            HIPCHECK(hipEventRecord(e0, 0));
-            chol_factor(0, dA, m_pad, m_pad, 1, de, Wd, fl);
-            HIPCHECK(hipEventRecord(e1, 0));
-            chol_bsolve(0, dA, m_pad, m_pad, Wd, dA + (size_t)m_pad * m_pad, W, 1, fl, de);
-            HIPCHECK(hipEventRecord(e2, 0));
-            HIPCHECK(hipEventSynchronize(e2));
-            float a = 0, b = 0;
-            HIPCHECK(hipEventElapsedTime(&a, e0, e1));
-            HIPCHECK(hipEventElapsedTime(&b, e1, e2));
-            if (it > 0) {
-                tf += a;
-                ts += b;
-            }
-        }
-        *ms_factor = tf / reps;
-        *ms_solve = ts / reps;
-        if (trace) {
-            const size_t nts = (size_t)32 * (m_pad / kNB + 1);
-            unsigned long long *dt = dalloc<unsigned long long>(nts, owned);
-            HIPCHECK(hipMemset(dt, 0, nts * sizeof(unsigned long long)));
-            HIPCHECK(hipMemcpy(dA, src, h.size() * sizeof(double), hipMemcpyDeviceToDevice));
-            chol_factor(0, dA, m_pad, m_pad, 1, de, Wd, fl, dt);
-            HIPCHECK(hipDeviceSynchronize());
-            HIPCHECK(hipMemcpy(trace, dt, nts * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipEventDestroy(e2);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_gram(double *C, const double *Yh, const double *wh, int n, int k) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_pad = round_up(n, kGramTile);
-        const int k_pad = round_up(k, 256);
-        double *dY = dalloc<double>((size_t)n_pad * k_pad, owned);
-        double *dw = dalloc<double>(k_pad, owned);
-        HIPCHECK(hipMemcpy2D(dY, (size_t)n_pad * sizeof(double), Yh, (size_t)n * sizeof(double),
-                             (size_t)n * sizeof(double), (size_t)k, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dw, wh, (size_t)k * sizeof(double), hipMemcpyHostToDevice));
-        const int S = gram_splits_for(n_pad, k_pad);
-        const size_t stride = (size_t)n_pad * n_pad;
-        double *sl = dalloc<double>(stride * S, owned);
-        double *red = dalloc<double>(stride + n_pad, owned);
-        launch_gram(0, dY, n_pad, dw, n_pad, k_pad, S, sl, n_pad, stride);
-        launch_slab_sum(0, sl, S, stride, n_pad, nullptr, 0, red, 1);
-        HIPCHECK(hipGetLastError());
-        std::vector<double> h(tri_count(n_pad));
-        HIPCHECK(hipMemcpy(h.data(), red, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int c = 0; c < n; ++c)
-            for (int r = 0; r < n; ++r)
-                C[(size_t)r + (size_t)c * n] = r <= c ? h[tri_index(r, c)] : h[tri_index(c, r)];
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_gram_ozaki(double *C, const double *Yh, const double *wh, int n, int k) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_pad = round_up(n, kGramTile);
-        const int n_oz = oz_rows(n_pad);
-        const int k_pad = round_up(k, 256);
-        const int nkc = k_pad / kOzKC;
-        double *dY = dalloc<double>((size_t)n_pad * k_pad, owned);
-        double *dw = dalloc<double>(k_pad, owned);
-        HIPCHECK(hipMemcpy2D(dY, (size_t)n_pad * sizeof(double), Yh, (size_t)n * sizeof(double),
-                             (size_t)n * sizeof(double), (size_t)k, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dw, wh, (size_t)k * sizeof(double), hipMemcpyHostToDevice));
-        const int b = oz_bits_for(k_pad);
-        const int S = oz_splits_for(n_oz, nkc);
-        double *xmax = dalloc<double>((size_t)nkc * n_oz, owned);
-        double *rowmax = dalloc<double>((size_t)oz_bound_groups(k_pad) * n_oz, owned);
-        double *rscale = dalloc<double>(n_oz, owned);
-        int *escale = dalloc<int>(n_oz, owned);
-        int8_t *R = dalloc<int8_t>(oz_residue_bytes(n_oz, k_pad), owned);
-        int8_t *P = dalloc<int8_t>(oz_partial_bytes(n_oz, S), owned);
-        const size_t stride = (size_t)n_pad * n_pad;
-        double *red = dalloc<double>(stride + n_pad, owned);
-        launch_oz_xmax(0, dY, n_pad, n_pad, n_oz, k_pad, xmax);
-        launch_oz_scale(0, dw, k_pad, xmax, n_oz, b, rowmax, rscale, escale);
-        launch_oz_residues(0, dY, n_pad, n_pad, n_oz, k_pad, dw, rscale, R);
-        launch_oz_gemm(0, R, n_oz, k_pad, S, P);
-        launch_oz_crt(0, P, S, n_oz, n_pad, escale, nullptr, 0, red);
-        HIPCHECK(hipGetLastError());
-        std::vector<double> h(tri_count(n_pad));
-        HIPCHECK(hipMemcpy(h.data(), red, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int c = 0; c < n; ++c)
-            for (int r = 0; r < n; ++r)
-                C[(size_t)r + (size_t)c * n] = r <= c ? h[tri_index(r, c)] : h[tri_index(c, r)];
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_sparse_gram(double *C, double *xu, const int *colptr, const int *rowidx, const double *val,
-                   const double *D, const double *u, int n, int p) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_pad = round_up(n, kGramTile);
-        SparseDesign sd;
-        sd.build(0, n, n_pad, p, colptr, rowidx, val, owned);
-        double *dD = dalloc<double>(p, owned), *du = dalloc<double>(p, owned);
-        HIPCHECK(hipMemcpy(dD, D, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
-        if (u) HIPCHECK(hipMemcpy(du, u, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
-        double *tri = dalloc<double>(tri_count(n_pad), owned);
-        double *dxu = dalloc<double>(n_pad, owned);
-        sd.gram(0, dD, du, tri, dxu);
-        HIPCHECK(hipGetLastError());
-        std::vector<double> h(tri_count(n_pad));
-        HIPCHECK(hipMemcpy(h.data(), tri, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int c = 0; c < n; ++c)
-            for (int r = 0; r < n; ++r)
-                C[(size_t)r + (size_t)c * n] = r <= c ? h[tri_index(r, c)] : h[tri_index(c, r)];
-        if (xu) HIPCHECK(hipMemcpy(xu, dxu, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_bench_sparse_gram(const int *colptr, const int *rowidx, const double *val, const double *D,
-                         int n, int p, int reps, double *ms_gram, double *ms_rows,
-                         long long *pairs) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_pad = round_up(n, kGramTile);
-        SparseDesign sd;
-        sd.build(0, n, n_pad, p, colptr, rowidx, val, owned);
-        double *dD = dalloc<double>(p, owned), *du = dalloc<double>(p, owned);
-        HIPCHECK(hipMemcpy(dD, D, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
-        double *tri = dalloc<double>(tri_count(n_pad), owned);
-        double *dxu = dalloc<double>(n_pad, owned);
-        hipEvent_t e0, e1, e2;
-        HIPCHECK(hipEventCreate(&e0));
-        HIPCHECK(hipEventCreate(&e1));
-        HIPCHECK(hipEventCreate(&e2));
-        sd.gram(0, dD, du, tri, dxu);  // warm
-        float tg = 0, tr = 0;
-        for (int r = 0; r < reps; ++r) {
-            HIPCHECK(hipEventRecord(e0, 0));
-            if (sd.col_mode)
-                sd.gram(0, dD, du, tri, dxu);
-            else
-                launch_sp_gram(0, sd.estart, sd.prod, sd.pj, dD, n_pad, tri);
-            HIPCHECK(hipEventRecord(e1, 0));
-            if (!sd.col_mode)
-                launch_sp_rows(0, sd.rowptr, sd.colidx, sd.rval, n_pad, du, dD, dxu, tri);
-            HIPCHECK(hipEventRecord(e2, 0));
-            HIPCHECK(hipEventSynchronize(e2));
-            float a = 0, b = 0;
-            HIPCHECK(hipEventElapsedTime(&a, e0, e1));
-            HIPCHECK(hipEventElapsedTime(&b, e1, e2));
-            tg += a;
-            tr += b;
-        }
-        *ms_gram = tg / reps;
-        *ms_rows = tr / reps;
-        if (pairs) *pairs = (long long)sd.pairs;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipEventDestroy(e2);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_bench_ozaki(int n, int k, int nsplit, int dbg, int reps, double *ms) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_oz = oz_rows(round_up(n, kGramTile));
-        const int k_pad = round_up(k, 256);
-        const int S = nsplit > 0 ? nsplit : oz_splits_for(n_oz, k_pad / kOzKC);
-        int8_t *R = dalloc<int8_t>(oz_residue_bytes(n_oz, k_pad), owned);
-        int8_t *P = dalloc<int8_t>(oz_partial_bytes(n_oz, S), owned);
-        // random residues in [-120, 120]
-        std::vector<int8_t> h(oz_residue_bytes(n_oz, k_pad));
-        uint64_t st = 0x9E3779B97F4A7C15ULL;
-        for (auto &v : h) {
-            st = st * 6364136223846793005ULL + 1442695040888963407ULL;
-            v = (int8_t)((int)((st >> 33) % 241) - 120);
-        }
-        HIPCHECK(hipMemcpy(R, h.data(), h.size(), hipMemcpyHostToDevice));
-        hipEvent_t e0, e1;
-        HIPCHECK(hipEventCreate(&e0));
-        HIPCHECK(hipEventCreate(&e1));
-        // dbg 999: production kernel without K rotation; 1000 + L: with pair lead L / 1000;
-        // 1000000 + 1000 T + L: lead L / 1000 and late shift T / 1000
-        int lead = kOzLeadDefault, late = -1;
-        if (dbg == 999 || (dbg >= 1000 && dbg < 2000)) {
-            lead = dbg == 999 ? -1 : dbg - 1000;
-            dbg = 0;
-        } else if (dbg >= 1000000) {
-            lead = dbg % 1000;
-            late = (dbg / 1000) % 1000;
-            dbg = 0;
-        }
-        launch_oz_gemm(0, R, n_oz, k_pad, S, P, dbg, lead, late);
-        HIPCHECK(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; ++r) launch_oz_gemm(0, R, n_oz, k_pad, S, P, dbg, lead, late);
-        HIPCHECK(hipEventRecord(e1, 0));
-        HIPCHECK(hipEventSynchronize(e1));
-        float t = 0;
-        HIPCHECK(hipEventElapsedTime(&t, e0, e1));
-        *ms = t / reps;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-int bb_chol_solve(double *x, const double *Ah, const double *bh, int m, int nrhs) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        if (nrhs < 1 || nrhs > 2) throw HipError("nrhs must be 1 or 2");
-        HIPCHECK(hipSetDevice(g_device));
-        const int m_pad = round_up(m, kNB);
-        double *dA = dalloc<double>((size_t)m_pad * (m_pad + kNB), owned);
-        // identity padding, then the user block and the RHS (forward-solved in place)
-        std::vector<double> h((size_t)m_pad * (m_pad + kNB), 0.0);
-        for (int c = 0; c < m_pad; ++c)
-            for (int r = 0; r <= c; ++r)
-                h[(size_t)r + (size_t)c * m_pad] =
-                    (r < m && c < m) ? Ah[(size_t)r + (size_t)c * m] : (r == c ? 1.0 : 0.0);
-        for (int q = 0; q < nrhs; ++q)
-            for (int r = 0; r < m; ++r) h[(size_t)r + (size_t)(m_pad + q) * m_pad] = bh[r + (size_t)q * m];
-        HIPCHECK(hipMemcpy(dA, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-        double *Wd = dalloc<double>(chol_wd_words(m_pad), owned);
-        unsigned int *fl = dalloc<unsigned int>(chol_flag_words(m_pad, 1), owned);
-        double *W = dalloc<double>((size_t)m_pad * nrhs, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-        chol_factor(0, dA, m_pad, m_pad, 1, de, Wd, fl);
-        chol_bsolve(0, dA, m_pad, m_pad, Wd, dA + (size_t)m_pad * m_pad, W, nrhs, fl, de);
-        HIPCHECK(hipGetLastError());
-        std::vector<double> hw((size_t)m_pad * nrhs);
-        HIPCHECK(hipMemcpy(hw.data(), W, hw.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int q = 0; q < nrhs; ++q)
-            for (int r = 0; r < m; ++r) x[r + (size_t)q * m] = hw[r + (size_t)q * m_pad];
-        uint32_t f = 0;
-        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
-        if (f & 8u) {
-            set_error("matrix is not positive definite");
-            rc = -3;
-        }
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------
-// Bridge EM (restating BR::EM, Code/C/BridgeRegression.cpp:600-708, with sig = 1 and
-// tau = ratio as the EM wrapper passes them, BridgeWrapper.cpp:57-73).  X'X and X'y are
-// formed once on the device; every maximisation step assembles the masked system on the
-// device (k_em_form), factors it with the persistent Cholesky and back-solves, or runs
-// conjugate gradients (k_em_cg).  The expectation step (lambda_j, the active set, the
-// distance) is an O(p) host loop over the same order as the reference.
-// Returns the number of "solves" (total_iter) or, when every coefficient was dropped, the
-// EM iteration count (the reference's early `return iter`); -1 after an error.
-// ---------------------------------------------------------------------------
-int bb_bridge_em(double *beta_out, const double *yh, const double *Xh, int n, int p, double ratio,
-                 double alpha, double lambda_max, double tol, int max_iter, int use_cg) {
-    std::vector<void *> owned;
-    int ret = -1;
-    std::fill(beta_out, beta_out + p, 0.0);
-    try {
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_pad = round_up(n, kGramTile), p_pad = round_up(p, 256);
-        double *dX = dalloc<double>((size_t)n_pad * p_pad, owned);
-        double *dy = dalloc<double>(n_pad, owned);
-        HIPCHECK(hipMemcpy2D(dX, (size_t)n_pad * sizeof(double), Xh, (size_t)n * sizeof(double),
-                             (size_t)n * sizeof(double), (size_t)p, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dy, yh, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        // G = X'X (transpose, Gram over rows with unit weights), b = X'y
-        double *Xt = dalloc<double>((size_t)p_pad * n_pad, owned);
-        launch_transpose(0, dX, n_pad, n_pad, p_pad, Xt, p_pad);
-        double *ones = dalloc<double>(n_pad, owned);
-        {
-            std::vector<double> h1(n_pad, 1.0);
-            HIPCHECK(hipMemcpy(ones, h1.data(), n_pad * sizeof(double), hipMemcpyHostToDevice));
-        }
-        const int Sg = gram_splits_for(p_pad, n_pad);
-        const size_t gstride = (size_t)p_pad * p_pad;
-        double *sl = dalloc<double>(gstride * Sg, owned);
-        launch_gram(0, Xt, p_pad, ones, p_pad, n_pad, Sg, sl, p_pad, gstride);
-        double *G = dalloc<double>(gstride + p_pad, owned);
-        launch_slab_sum(0, sl, Sg, gstride, p_pad, nullptr, 0, G, 0);
-        double *bvec = dalloc<double>(p_pad, owned);
-        launch_coldot(0, dX, n_pad, n_pad, dy, p, bvec);
-        double *A = dalloc<double>((size_t)p_pad * (p_pad + kNB), owned);
-        double *Wd = dalloc<double>(chol_wd_words(p_pad), owned);
-        unsigned int *fl = dalloc<unsigned int>(chol_flag_words(p_pad, 1), owned);
-        double *W = dalloc<double>(p_pad, owned);
-        double *dlam = dalloc<double>(p_pad, owned);
-        int *dmask = dalloc<int>(p_pad, owned);
-        double *work = dalloc<double>((size_t)3 * p_pad, owned);
-        int *dit = dalloc<int>(1, owned);
-        uint32_t *de = dalloc<uint32_t>(1, owned);
-
-        std::vector<int> mask(p, 1);
-        std::vector<double> nb(p_pad, 0.0), ob(p, 0.0), lam(p_pad, 0.0);
-        auto upload_mask = [&]() {
-            std::vector<int> m(p_pad, 0);
-            std::copy(mask.begin(), mask.end(), m.begin());
-            HIPCHECK(hipMemcpy(dmask, m.data(), p_pad * sizeof(int), hipMemcpyHostToDevice));
-        };
-        // direct maximisation: A = XX_act (+ c2 diag(lam)), solve by Cholesky (symsolve)
-        auto solve_direct = [&](bool with_lam) {
-            launch_em_form(0, G, p_pad, with_lam ? dlam : nullptr, dmask, bvec, p, p_pad, A,
-                           p_pad, p_pad);
-            HIPCHECK(hipMemset(de, 0, sizeof(uint32_t)));
-            chol_factor(0, A, p_pad, p_pad, 1, de, Wd, fl);
-            chol_bsolve(0, A, p_pad, p_pad, Wd, A + (size_t)p_pad * p_pad, W, 1, fl, de);
-            HIPCHECK(hipGetLastError());
-            uint32_t f = 0;
-            HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
-            if (f & 8u) throw HipError("symsolve: matrix is not positive definite");
-            if (f) throw HipError("device solver reported an error");
-            HIPCHECK(hipMemcpy(nb.data(), W, p_pad * sizeof(double), hipMemcpyDeviceToHost));
-        };
-        const double sig = 1.0, tau = ratio;
-        const double c1 = alpha * std::exp((2 - alpha) * (std::log(tau) - std::log(sig)));
-        const double c2 = std::exp(-2 * (std::log(tau) - std::log(sig)));
-        int pa = p;             // active count
-        long total_iter = p;    // the first symsolve
-        upload_mask();
-        solve_direct(false);    // one maximisation step with A = X'X
-        double dist = tol + 1.0;
-        int iter = 0;
-        while (dist > tol && iter < max_iter) {
-            // expectation step over the active coordinates, in order
-            int num = 0;
-            for (int j = 0; j < p; ++j) {
-                if (!mask[j]) continue;
-                const double l = c1 * std::exp((alpha - 2) * std::log(std::fabs(nb[j])));
-                if (l < lambda_max) {
-                    lam[j] = c2 * l;
-                    ob[j] = nb[j];
-                    ++num;
-                } else {
-                    mask[j] = 0;
-                }
-            }
-            if (num < pa) {
-                if (num == 0) {
-                    ret = iter;
-                    for (void *q : owned) (void)hipFree(q);
-                    owned.clear();
-                    return ret;
-                }
-                pa = num;
-                upload_mask();
-            }
-            HIPCHECK(hipMemcpy(dlam, lam.data(), p_pad * sizeof(double), hipMemcpyHostToDevice));
-            if (!use_cg) {
-                solve_direct(true);
-                total_iter += pa;
-            } else {
-                // x0 = old beta on the active set (0 elsewhere)
-                std::vector<double> x0(p_pad, 0.0);
-                for (int j = 0; j < p; ++j)
-                    if (mask[j]) x0[j] = ob[j];
-                HIPCHECK(hipMemcpy(W, x0.data(), p_pad * sizeof(double), hipMemcpyHostToDevice));
-                launch_em_form(0, G, p_pad, dlam, dmask, bvec, p, p_pad, A, p_pad, p_pad);
-                launch_em_cg(0, A, p_pad, p_pad, A + (size_t)p_pad * p_pad, W, tol, pa, work,
-                             dit);
-                HIPCHECK(hipGetLastError());
-                int it = 0;
-                HIPCHECK(hipMemcpy(&it, dit, sizeof(int), hipMemcpyDeviceToHost));
-                HIPCHECK(hipMemcpy(nb.data(), W, p_pad * sizeof(double), hipMemcpyDeviceToHost));
-                total_iter += it;
-            }
-            double d2 = 0.0;
-            for (int j = 0; j < p; ++j)
-                if (mask[j]) d2 += (nb[j] - ob[j]) * (nb[j] - ob[j]);
-            dist = std::sqrt(d2);
-            ++iter;
-        }
-        for (int j = 0; j < p; ++j) beta_out[j] = mask[j] ? nb[j] : 0.0;
-        ret = (int)total_iter;
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        std::fill(beta_out, beta_out + p, 0.0);
-        ret = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return ret;
-}
-
-// Batched EM over `count` ratios (trace.beta), direct solves: X'X and X'y once, then one
-// launch in which a workgroup per ratio runs the whole EM -- k_em_batch (system in LDS) for
-// p <= 128, k_em_batch_tiled (system in a global scratch slice per ratio, tiled Cholesky)
-// above, the ratios in chunks whose scratch fits min(free / 2, 16 GiB).
-// beta: count x p (row r = ratio r); solves: count (as bb_bridge_em returns, -1 on a
-// non positive-definite system).  Returns 0, or -1 with bb_last_error().
-int bb_bridge_em_batch(double *beta, int *solves, const double *yh, const double *Xh, int n,
-                       int p, const double *ratios, const double *lambda_max, int count,
-                       double alpha, double tol, int max_iter) {
-    std::vector<void *> owned;
-    int rc = 0;
-    try {
-        if (p < 1) throw HipError("bb_bridge_em_batch: needs p >= 1");
-        if (count < 1) throw HipError("bb_bridge_em_batch: empty ratio grid");
-        HIPCHECK(hipSetDevice(g_device));
-        const int n_pad = round_up(n, kGramTile), p_pad = round_up(p, 256);
-        double *dX = dalloc<double>((size_t)n_pad * p_pad, owned);
-        double *dy = dalloc<double>(n_pad, owned);
-        HIPCHECK(hipMemcpy2D(dX, (size_t)n_pad * sizeof(double), Xh, (size_t)n * sizeof(double),
-                             (size_t)n * sizeof(double), (size_t)p, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dy, yh, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        double *Xt = dalloc<double>((size_t)p_pad * n_pad, owned);
-        launch_transpose(0, dX, n_pad, n_pad, p_pad, Xt, p_pad);
-        double *ones = dalloc<double>(n_pad, owned);
-        {
-            std::vector<double> h1(n_pad, 1.0);
-            HIPCHECK(hipMemcpy(ones, h1.data(), n_pad * sizeof(double), hipMemcpyHostToDevice));
-        }
-        const int Sg = gram_splits_for(p_pad, n_pad);
-        const size_t gstride = (size_t)p_pad * p_pad;
-        double *sl = dalloc<double>(gstride * Sg, owned);
-        launch_gram(0, Xt, p_pad, ones, p_pad, n_pad, Sg, sl, p_pad, gstride);
-        double *G = dalloc<double>(gstride + p_pad, owned);
-        launch_slab_sum(0, sl, Sg, gstride, p_pad, nullptr, 0, G, 0);
-        double *bvec = dalloc<double>(p_pad, owned);
-        launch_coldot(0, dX, n_pad, n_pad, dy, p, bvec);
-        double *dr = dalloc<double>(count, owned), *dl = dalloc<double>(count, owned);
-        HIPCHECK(hipMemcpy(dr, ratios, count * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(dl, lambda_max, count * sizeof(double), hipMemcpyHostToDevice));
-        double *db = dalloc<double>((size_t)count * p, owned);
-        int *ds = dalloc<int>(count, owned);
-        if (p <= 128) {
-            launch_em_batch(0, G, p_pad, bvec, p, dr, dl, count, alpha, tol, max_iter, db, ds);
-            HIPCHECK(hipGetLastError());
-        } else {
-            const int pe = round_up(p, em_tile());
-            const size_t per = (size_t)pe * pe * sizeof(double);
-            size_t fr = 0, tot = 0;
-            HIPCHECK(hipMemGetInfo(&fr, &tot));
-            const size_t budget = std::min(fr / 2, (size_t)16 << 30);
-            const int chunk = (int)std::max<size_t>(1, std::min<size_t>(count, budget / per));
-            if (per > fr) throw HipError("bb_bridge_em_batch: p x p system does not fit");
-            double *scr = dalloc<double>((size_t)chunk * pe * pe, owned);
-            double *vec = dalloc<double>((size_t)chunk * 3 * pe, owned);
-            int *msk = dalloc<int>((size_t)chunk * pe, owned);
-            for (int r0 = 0; r0 < count; r0 += chunk) {
-                launch_em_batch_tiled(0, G, p_pad, bvec, p, pe, dr, dl, r0,
-                                      std::min(chunk, count - r0), alpha, tol, max_iter, scr, vec,
-                                      msk, db, ds);
-                HIPCHECK(hipGetLastError());
-            }
-        }
-        HIPCHECK(hipMemcpy(beta, db, (size_t)count * p * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(solves, ds, count * sizeof(int), hipMemcpyDeviceToHost));
-    } catch (std::exception &ex) {
-        set_error("%s", ex.what());
-        rc = -1;
-    }
-    for (void *q : owned) (void)hipFree(q);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------
-// Reference .C entry points
-// ---------------------------------------------------------------------------
-// BridgeWrapper.cpp:738-756: flags NaN / +Inf / -Inf / NA in x[0] and sets x[0] = NA when
-// it is 0 (a marshalling test of R's special values; host only).
-void mytest(int *out, double *x) {
-    const uint64_t na_bits = 0x7FF00000000007A2ull;  // R's NA_REAL
-    uint64_t bits;
-    memcpy(&bits, x, sizeof(bits));
-    out[0] = 0;
-    if (std::isnan(x[0])) out[0] = 1;
-    if (x[0] == HUGE_VAL) out[0] = 2;
-    if (x[0] == -HUGE_VAL) out[0] = 3;
-    if (std::isnan(x[0]) && (uint32_t)bits == 1954u) out[0] = 4;
-    if (x[0] == 0.0) memcpy(x, &na_bits, sizeof(na_bits));
-}
-
-static void trunc_call(int mode, int num, double *x, const double *p0, const double *p1,
-                       const double *p2, const double *p3, const char *name) {
-    uint64_t k0, k1;
-    next_call_key(&k0, &k1);
-    if (bb_trunc_batch(mode, num, x, p0, p1, p2, p3, k0, k1) != 0)
-        fprintf(stderr, "Error: %s: %s\n", name, g_last_error.c_str());
-}
-
-// BridgeWrapper.cpp:843-935 (decl. BridgeWrapper.h:236-242)
-void rtnorm_left(double *x, double *left, double *mu, double *sig, int *num) {
-    trunc_call(0, *num, x, left, mu, sig, nullptr, "rtnorm_left");
-}
-void rtnorm_both(double *x, double *left, double *right, double *mu, double *sig, int *num) {
-    trunc_call(1, *num, x, left, right, mu, sig, "rtnorm_both");
-}
-void rtnorm(double *x, double *left, double *right, double *mu, double *sig, int *num) {
-    trunc_call(2, *num, x, left, right, mu, sig, "rtnorm");
-}
-// BridgeWrapper.cpp:762-830 (decl. BridgeWrapper.h:230-234)
-void rtexpon_rate_left(double *x, double *left, double *rate, int *num) {
-    trunc_call(3, *num, x, left, rate, nullptr, nullptr, "rtexpon_rate_left");
-}
-void rtexpon_rate_both(double *x, double *left, double *right, double *rate, int *num) {
-    trunc_call(4, *num, x, left, right, rate, nullptr, "rtexpon_rate_both");
-}
-void rtexpon_rate(double *x, double *left, double *right, double *rate, int *num) {
-    trunc_call(5, *num, x, left, right, rate, nullptr, "rtexpon_rate");
-}
-
-// BridgeWrapper.cpp:944-962 (decl. BridgeWrapper.h:242); `scale` carries the shape, as
-// rrtgamma (BridgeWrapper.R:482-509) passes it.
-void rrtgamma_rate(double *x, double *scale, double *rate, double *right_t, int *num) {
-    uint64_t k0, k1;
-    next_call_key(&k0, &k1);
-    if (bb_rrtgamma_batch(*num, x, scale, rate, right_t, k0, k1) != 0)
-        fprintf(stderr, "Error: rrtgamma_rate: %s\n", g_last_error.c_str());
-}
-
-void retstable_LD(double *x, double *alpha, double *V0, double *h, int *num) {
-    uint64_t k0, k1;
-    next_call_key(&k0, &k1);
-    int rc = bb_retstable_batch(x, alpha, V0, h, *num, k0, k1, 0, 0);
-    if (rc != 0) fprintf(stderr, "Error: retstable_LD: %s\n", g_last_error.c_str());
-}
-
-// BridgeWrapper.cpp:544-568 (decl. BridgeWrapper.h:166-176); R passes use.cg through
-// as.integer, so it is read as int (BridgeWrapper.R:116-123).  max_iter returns the number
-// of solves; errors print as the reference's EM wrapper does (BridgeWrapper.cpp:64-70).
-void bridge_EM(double *betap, const double *yp, const double *Xp, const double *ratio,
-               const double *alpha, const int *P, const int *N, const double *lambda_max,
-               const double *tol, int *max_iter, const int *use_cg) {
-    if (*use_cg && g_verbose) printf("Using conjugate gradient method.\n");
-    const int it = bb_bridge_em(betap, yp, Xp, *N, *P, *ratio, *alpha, *lambda_max, *tol,
-                                *max_iter, *use_cg);
-    if (it < 0) {
-        printf("Error: %s\n", g_last_error.c_str());
-        printf("Aborting EM.\n");
-    }
-    *max_iter = it;
-}
 
 }  // extern "C"
 
@@ -3794,10 +2687,11 @@ bb_config stable_call_config(const double *sig2_shape, const double *sig2_scale,
 }
 
 // Trace ring slots for M samples of p_local coefficients (`ntr` p-long traces per slot):
-// the whole run if it fits the per-engine budget, else a ring copied out in chunks.
-int ring_capacity(int m, int p_local, int ntr) {
+// the whole run if it fits the per-engine budget, else a ring copied out in chunks.  The
+// `chains` rings of a chain batch share the budget: each gets a chains-th.
+int ring_capacity(int m, int p_local, int ntr, int chains = 1) {
     const size_t per = (size_t)ntr * p_local * sizeof(double) + 3 * sizeof(double);
-    size_t cap = g_trace_budget / (per ? per : 1);
+    size_t cap = g_trace_budget / ((size_t)chains * per);
     if (cap < 16) cap = 16;
     return (int)std::min<size_t>(cap, (size_t)(m < 1 ? 1 : m));
 }
@@ -3848,16 +2742,15 @@ struct Chain {
         ahead.mark(eng[0]->stream);
     }
     // trace slots [slot0, slot0 + count) -> samples [s0, s0 + count) of the P x M outputs
-    int copy_out(int slot0, int count, int s0, double *beta, double *lam, double *sig2,
-                 double *tau, double *alpha, double *u = nullptr, double *shape = nullptr) {
+    int copy_out(int slot0, int count, int s0, const Traces &o) {
         if (count <= 0) return 0;
         const size_t P = (size_t)p;
         if (eng.size() == 1) {
-            int rc = bb_engine_get_trace(eng[0], slot0, count, beta + s0 * P, lam + s0 * P,
-                                         sig2 ? sig2 + s0 : nullptr, tau + s0, alpha + s0);
-            if (rc == 0 && (u || shape))
-                rc = bb_engine_get_tri_trace(eng[0], slot0, count, u ? u + s0 * P : nullptr,
-                                             shape ? shape + s0 * P : nullptr);
+            int rc = bb_engine_get_trace(eng[0], slot0, count, o.beta + s0 * P, o.lam + s0 * P,
+                                         o.sig2 ? o.sig2 + s0 : nullptr, o.tau + s0, o.alpha + s0);
+            if (rc == 0 && (o.u || o.shape))
+                rc = bb_engine_get_tri_trace(eng[0], slot0, count, o.u ? o.u + s0 * P : nullptr,
+                                             o.shape ? o.shape + s0 * P : nullptr);
             return rc;
         }
         for (size_t r = 0; r < eng.size(); ++r) {
@@ -3866,12 +2759,12 @@ struct Chain {
             std::vector<double> b(pl * count), l(pl * count);
             (void)hipSetDevice(e->cfg.device);
             if (bb_engine_get_trace(e, slot0, count, b.data(), l.data(),
-                                    r == 0 && sig2 ? sig2 + s0 : nullptr,
-                                    r == 0 ? tau + s0 : nullptr, r == 0 ? alpha + s0 : nullptr))
+                                    r == 0 && o.sig2 ? o.sig2 + s0 : nullptr,
+                                    r == 0 ? o.tau + s0 : nullptr, r == 0 ? o.alpha + s0 : nullptr))
                 return -1;
             for (int k = 0; k < count; ++k) {
-                memcpy(beta + (s0 + k) * P + j0s[r], &b[k * pl], pl * sizeof(double));
-                memcpy(lam + (s0 + k) * P + j0s[r], &l[k * pl], pl * sizeof(double));
+                memcpy(o.beta + (s0 + k) * P + j0s[r], &b[k * pl], pl * sizeof(double));
+                memcpy(o.lam + (s0 + k) * P + j0s[r], &l[k * pl], pl * sizeof(double));
             }
         }
         return 0;
@@ -3972,25 +2865,29 @@ Outcome drive_schedule(C &ch, int kBlock, int nburn, uint64_t t_base, int m, int
     return OUT_OK;
 }
 
-Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, double *betap,
-                    double *lambdap, double *sig2p, double *taup, double *alphap,
-                    double *runtime, double *up = nullptr, double *shapep = nullptr) {
+// "Error: <message>" and the line the reference's samplers end on after an error
+__attribute__((format(printf, 1, 2))) void print_abort(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    printf("Error: ");
+    vprintf(fmt, ap);
+    va_end(ap);
+    printf("\nAborting Gibbs sampler.\n");
+    fflush(stdout);
+}
+
+Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, const Traces &out,
+                    double *runtime) {
     // BridgeWrapper.cpp:273-275, 295-297 poll every 10 sweeps.  A fused engine runs a
     // whole block in one launch at ~15-30 us per sweep, so it polls every 50 (< 2 ms) and
     // pays the launch and LDS-staging prologue once per 50 sweeps instead of per 10.
     const int kBlock = ch.fused() ? 50 : 10;
     return drive_schedule(
         ch, kBlock, nburn, t_base, m, b, runtime,
-        [&](int slot0, int count, int s0) {
-            return ch.copy_out(slot0, count, s0, betap, lambdap, sig2p, taup, alphap, up, shapep);
-        },
+        [&](int slot0, int count, int s0) { return ch.copy_out(slot0, count, s0, out); },
         [&] {
             const uint32_t f = ch.flags();
-            if (f & ~4u) {
-                printf("Error: numerical failure in the device sampler (flags %u)\n", f);
-                printf("Aborting Gibbs sampler.\n");
-                fflush(stdout);
-            }
+            if (f & ~4u) print_abort("numerical failure in the device sampler (flags %u)", f);
         });
 }
 
@@ -4004,50 +2901,59 @@ void print_banner(const char *title, const bb_config &c, int b, int m) {
     printf("\nBurn-in: %i, Num. Samples: %i\n", b, m);
 }
 
-// The stable-family .C driver (BridgeWrapper.cpp:207-313 / :434-537): B + 1 burn-in sweeps
-// in slot 0, MCMC sample i at t = B + 1 + i.  Errors print and return partial traces.
+// What tells the samplers' .C calls apart: the banner's title, the p-long traces per ring slot
+// and the schedule -- `nburn` burn-in sweeps in slot 0, MCMC sample i at t = t_base + i.
+struct CallKind {
+    const char *title;
+    int ntr, nburn;
+    uint64_t t_base;
+};
+// the stable family (BridgeWrapper.cpp:207-313 / :434-537): B + 1 burn-in sweeps
+CallKind stable_kind(int b, const char *title = "Bridge Regression (mix. of normals):") {
+    return {title, 2, b + 1, (uint64_t)b + 1};
+}
+// the triangle mixture (BridgeWrapper.cpp:80-204 / :320-432): `burn` sweeps; a slot is 4
+// P-vectors (beta, u, omega, shape)
+CallKind tri_kind(int b) {
+    return {"Bridge Regression (mix. of triangles):", 4, b, (uint64_t)b};
+}
+
+// One chain of a .C sampler call over the engines `create` makes.  Errors print and return
+// partial traces.
 template <class Create>
-Outcome stable_call(const bb_config &c, Create create, int b, double *betap, double *lambdap,
-                    double *sig2p, double *taup, double *alphap, double *runtime,
-                    const char *title) {
+Outcome sampler_call(const CallKind &kd, const bb_config &c, int b, Create create,
+                     const Traces &out, double *runtime) {
     const int m = c.trace_capacity;
-    print_banner(title, c, b, m);
+    print_banner(kd.title, c, b, m);
     g_last_interrupted = 0;
     Outcome o;
     {
         Chain ch;
-        if (chain_build(ch, c, 2, create) != 0) {
-            printf("Error: %s\n", g_last_error.c_str());
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
+        if (chain_build(ch, c, kd.ntr, create) != 0) {
+            print_abort("%s", g_last_error.c_str());
             *runtime = 0.0;
             return OUT_ERROR;
         }
         g_last_devices = (int)ch.eng.size();
         g_last_capacity = ch.cap;
-        o = drive_chain(ch, b + 1, (uint64_t)b + 1, m, b, betap, lambdap, sig2p, taup, alphap,
-                        runtime);
-        if (o == OUT_ERROR) {
-            printf("Error: %s\n", g_last_error.c_str());
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-        }
+        o = drive_chain(ch, kd.nburn, kd.t_base, m, b, out, runtime);
+        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
     }
     if (g_verbose && o == OUT_OK) printf("Sampling complete: %g sec. for %i iterations.\n", *runtime, m);
     g_last_interrupted = o == OUT_INTERRUPTED;
     return o;
 }
 
-Outcome stable_dense(const bb_config &c, const double *yp, const double *Xp, int b,
-                     double *betap, double *lambdap, double *sig2p, double *taup, double *alphap,
-                     double *runtime, const char *title) {
+// ... over a dense column-major X (a shard takes its columns)
+Outcome dense_call(const CallKind &kd, const bb_config &c, const double *yp, const double *Xp,
+                   int b, const Traces &out, double *runtime) {
     const int n = c.n;
-    return stable_call(
-        c,
+    return sampler_call(
+        kd, c, b,
         [&](const bb_config *cc, int j0, int, bb_engine **e) {
             return bb_engine_create(cc, Xp + (size_t)j0 * n, yp, e);
         },
-        b, betap, lambdap, sig2p, taup, alphap, runtime, title);
+        out, runtime);
 }
 
 // A chain batch as drive_schedule drives it: every run advances all K chains.
@@ -4064,18 +2970,12 @@ struct ChainsRun {
 
 // K chains of a small design as one batch on drive_chain's schedule (50-sweep blocks, as a
 // fused single chain).  The trace budget bounds the batch: each chain's ring gets a K-th.
-Outcome stable_chains_batch(const bb_config &c0, int K, const double *yp, const double *Xp, int b,
-                            double *betap, double *lambdap, double *sig2p, double *taup,
-                            double *alphap, double *runtime) {
+Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const double *yp,
+                     const double *Xp, int b, const Traces &out, double *runtime) {
     const int m = c0.trace_capacity;
     *runtime = 0.0;
     bb_config c = c0;
-    {
-        const size_t per = (size_t)2 * c.p * sizeof(double) + 3 * sizeof(double);
-        size_t cap = g_trace_budget / (size_t)K / per;
-        if (cap < 16) cap = 16;
-        c.trace_capacity = (int)std::min<size_t>(cap, (size_t)(m < 1 ? 1 : m));
-    }
+    c.trace_capacity = ring_capacity(m, c.p, kd.ntr, K);
     bb_chains *raw = nullptr;
     if (bb_chains_create(&c, K, Xp, yp, &raw) != 0) return OUT_ERROR;
     std::unique_ptr<bb_chains> ch(raw);
@@ -4083,9 +2983,9 @@ Outcome stable_chains_batch(const bb_config &c0, int K, const double *yp, const 
     g_last_capacity = ch->cap;
     ChainsRun run{raw, ch->cap};
     return drive_schedule(
-        run, 50, b + 1, (uint64_t)b + 1, m, b, runtime,
+        run, 50, kd.nburn, kd.t_base, m, b, runtime,
         [&](int slot0, int count, int s0) {
-            ch->copy_out(slot0, count, s0, m, betap, lambdap, sig2p, taup, alphap);
+            ch->copy_out(slot0, count, s0, m, out);
             return 0;
         },
         [&] {
@@ -4093,36 +2993,26 @@ Outcome stable_chains_batch(const bb_config &c0, int K, const double *yp, const 
             HIPCHECK(hipMemcpy(f.data(), ch->err, (size_t)K * sizeof(uint32_t),
                                hipMemcpyDeviceToHost));
             for (int k = 0; k < K; ++k)
-                if (f[k] & ~4u) {
-                    printf("Error: numerical failure in the device sampler (flags %u) in chain "
-                           "%i\n", f[k], k);
-                    printf("Aborting Gibbs sampler.\n");
-                    fflush(stdout);
-                }
+                if (f[k] & ~4u)
+                    print_abort("numerical failure in the device sampler (flags %u) in chain %i",
+                                f[k], k);
         });
 }
 
-// bridge_reg_stable_chains: the batch where the fused small chain applies, else the K chains
-// one after another through the single-chain driver on streams k1 + c.
-Outcome stable_chains(const bb_config &c, int K, const double *yp, const double *Xp, int b,
-                      double *betap, double *lambdap, double *sig2p, double *taup,
-                      double *alphap, double *runtime) {
-    const char *title = "Bridge Regression (mix. of normals):";
-    const size_t m = (size_t)c.trace_capacity, pm = (size_t)c.p * m;
+// bridge_reg_stable_chains / bridge_regression_chains: the batch where the fused small chain
+// applies, else the K chains one after another through the single-chain driver on streams
+// k1 + k.
+Outcome chains_call(const CallKind &kd, const bb_config &c, int K, const double *yp,
+                    const double *Xp, int b, const Traces &out, double *runtime) {
+    const int m = c.trace_capacity;
     *runtime = 0.0;
     if (chains_refusal(c) == nullptr) {
-        print_banner(title, c, b, (int)m);
+        print_banner(kd.title, c, b, m);
         g_last_interrupted = 0;
-        const Outcome o = stable_chains_batch(c, K, yp, Xp, b, betap, lambdap, sig2p, taup,
-                                              alphap, runtime);
-        if (o == OUT_ERROR) {
-            printf("Error: %s\n", g_last_error.c_str());
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-        }
+        const Outcome o = chains_batch(kd, c, K, yp, Xp, b, out, runtime);
+        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
         if (g_verbose && o == OUT_OK)
-            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime,
-                   (int)m, K);
+            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime, m, K);
         g_last_interrupted = o == OUT_INTERRUPTED;
         return o;
     }
@@ -4130,12 +3020,82 @@ Outcome stable_chains(const bb_config &c, int K, const double *yp, const double 
         bb_config ck = c;
         ck.stream = c.stream + (uint64_t)k;
         double rt = 0.0;
-        const Outcome o = stable_dense(ck, yp, Xp, b, betap + k * pm, lambdap + k * pm,
-                                       sig2p + k * m, taup + k * m, alphap + k * m, &rt, title);
+        const Outcome o = dense_call(kd, ck, yp, Xp, b, out.chain(k, c.p, m), &rt);
         *runtime += rt;
         if (o == OUT_INTERRUPTED) return o;
     }
     return OUT_OK;
+}
+
+Outcome stable_csc(const bb_config &c, const double *yp, const int *Xcolptr, const int *Xrowidx,
+                   const double *Xval, int b, const Traces &out, double *runtime) {
+    const int p = c.p, n = c.n;
+    if (p > n && !c.ortho) {
+        return sampler_call(
+            stable_kind(b), c, b,
+            [&](const bb_config *cc, int j0, int j1, bb_engine **e) {
+                // the shard's columns: colptr rebased to its first entry
+                std::vector<int> cp(j1 - j0 + 1);
+                for (int j = j0; j <= j1; ++j) cp[j - j0] = Xcolptr[j] - Xcolptr[j0];
+                return bb_engine_create_csc(cc, cp.data(), Xrowidx + Xcolptr[j0],
+                                            Xval + Xcolptr[j0], yp, e);
+            },
+            out, runtime);
+    }
+    // p <= n or the orthogonal design: the dense paths of bridge_reg_stable (least-squares
+    // start, p x p Cholesky or ortho draw) on the densified X, after the same validation as
+    // the sparse engine's
+    try {
+        csc_validate(n, p, Xcolptr, Xrowidx);
+    } catch (std::exception &ex) {
+        print_abort("%s", ex.what());
+        *runtime = 0.0;
+        return OUT_ERROR;
+    }
+    std::vector<double> Xd((size_t)n * p, 0.0);
+    for (int j = 0; j < p; ++j)
+        for (int q = Xcolptr[j]; q < Xcolptr[j + 1]; ++q) Xd[(size_t)j * n + Xrowidx[q]] = Xval[q];
+    return dense_call(stable_kind(b), c, yp, Xd.data(), b, out, runtime);
+}
+
+Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, Traces out,
+                   double *runtime) {
+    c.method = 6;
+    for (int i = 0; i < c.n; ++i)
+        if (!(yp[i] == 0.0 || yp[i] == 1.0)) {
+            print_abort("logistic bridge needs y in {0, 1} (y[%d] = %g)", i, yp[i]);
+            *runtime = 0.0;
+            return OUT_ERROR;
+        }
+    std::vector<double> sig2(c.trace_capacity);
+    out.sig2 = sig2.data();
+    return dense_call(
+        stable_kind(b, "Bridge Regression (logistic, Polya-Gamma mix. of normals):"), c, yp, Xp,
+        b, out, runtime);
+}
+
+// a chains entry's nchains, checked before a key is taken or an output is touched
+bool nchains_ok(const char *entry, int nchains) {
+    if (nchains >= 1) return true;
+    set_error("%s: nchains must be at least 1 (got %d)", entry, nchains);
+    printf("Error: %s\n", g_last_error.c_str());
+    fflush(stdout);
+    return false;
+}
+
+// bb_config of a .C bridge_regression call: stable_call_config with the triangle method
+bb_config tri_call_config(const double *sig2_shape, const double *sig2_scale,
+                          const double *nu_shape, const double *nu_rate, const double *alpha_a,
+                          const double *alpha_b, const double *true_sig2, const double *true_tau,
+                          const double *true_alpha, int p, int n, int m, const int *ortho,
+                          const int *betaburn, int nchains = 1) {
+    const int no = 0;
+    bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
+                                     true_sig2, true_tau, true_alpha, p, n, m, &no, nchains);
+    c.method = 4;
+    c.ortho = *ortho != 0;                       // bridge_regression_ortho, :320-432
+    c.betaburn = *betaburn > 0 ? *betaburn : 0;  // BridgeRegression.cpp:407
+    return c;
 }
 
 }  // namespace
@@ -4204,100 +3164,38 @@ int bb_set_chol_version(int version) {
     return 0;
 }
 int bb_set_tuning(int key, int value) {
-    switch (key) {
-        case 1: {
-            const int old = g_oz_res_nt;
-            if (value >= 0) g_oz_res_nt = value > 2 ? 2 : value;
+    // one row per key: its variable and the largest value it takes (1: a switch, any non-zero
+    // value turns it on).  A negative value only queries; every call returns the old value.
+    static const struct {
+        int key, *var, max;
+    } kKeys[] = {{1, &g_oz_res_nt, 2},  {2, &g_bxb_nt, 1},     {3, &g_sp_nt, 3},
+                 {6, &g_nid_kmax, 64},  {7, &g_lam_xu, 3},     {8, &g_nid_sync, 2},
+                 {9, &g_shard_proto, 1}, {10, &g_nid_mixed, 1}, {11, &g_nid_poll, 1},
+                 {12, &g_rs_xcd, 1},    {13, &g_lam_wave, 1},  {15, &g_lam_lend, 1},
+                 {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1}};
+    for (const auto &k : kKeys)
+        if (k.key == key) {
+            const int old = *k.var;
+            if (value >= 0) *k.var = std::min(value, k.max);
             return old;
         }
-        case 2: {
-            const int old = g_bxb_nt;
-            if (value >= 0) g_bxb_nt = value ? 1 : 0;
-            return old;
-        }
-        case 3: {
-            const int old = g_sp_nt;
-            if (value >= 0) g_sp_nt = value > 3 ? 3 : value;
-            return old;
-        }
-        case 4: {
-            const int old = g_lam_occ;
-            if (value >= 0) g_lam_occ = value & 15;
-            return old;
-        }
-        case 5: {
-            const int old = g_lam_lanes;
-            if (value == 0 || value == 4 || value == 8 || value == 16 || value == 32 || value == 64)
-                g_lam_lanes = value;
-            return old;
-        }
-        case 6: {
-            const int old = g_nid_kmax;
-            if (value >= 0) g_nid_kmax = value > 64 ? 64 : value;
-            return old;
-        }
-        case 7: {
-            const int old = g_lam_xu;
-            if (value >= 0) g_lam_xu = value > 3 ? 3 : value;
-            return old;
-        }
-        case 8: {
-            const int old = g_nid_sync;
-            if (value >= 0) g_nid_sync = value > 2 ? 2 : value;
-            return old;
-        }
-        case 10: {
-            const int old = g_nid_mixed;
-            if (value >= 0) g_nid_mixed = value ? 1 : 0;
-            return old;
-        }
-        case 9: {
-            const int old = g_shard_proto;
-            if (value >= 0) g_shard_proto = value ? 1 : 0;
-            return old;
-        }
-        case 11: {
-            const int old = g_nid_poll;
-            if (value >= 0) g_nid_poll = value ? 1 : 0;
-            return old;
-        }
-        case 16: {  // forced Chebyshev iterate count (benchmarking only; bb_nid.hip)
-            const int old = g_nid_force_k;
-            if (value >= 0) nid_set_force_k(value > 64 ? 64 : value);
-            return old;
-        }
-        case 12: {
-            const int old = g_rs_xcd;
-            if (value >= 0) g_rs_xcd = value ? 1 : 0;
-            return old;
-        }
-        case 13: {
-            const int old = g_lam_wave;
-            if (value >= 0) g_lam_wave = value ? 1 : 0;
-            return old;
-        }
-        case 20: {
-            const int old = g_bsolve_ll;
-            if (value >= 0) g_bsolve_ll = value ? 1 : 0;
-            return old;
-        }
-        case 17: {
-            const int old = g_nid_fold;
-            if (value >= 0) g_nid_fold = value > 2 ? 2 : value;
-            return old;
-        }
-        case 21: {
-            const int old = g_chains_packed;
-            if (value >= 0) g_chains_packed = value ? 1 : 0;
-            return old;
-        }
-        case 15: {
-            const int old = g_lam_lend;
-            if (value >= 0) g_lam_lend = value ? 1 : 0;
-            return old;
-        }
-        default: return -1;
+    if (key == 4) {  // a mask of four bits
+        const int old = g_lam_occ;
+        if (value >= 0) g_lam_occ = value & 15;
+        return old;
     }
+    if (key == 5) {  // a lane count the kernel has an instance of (anything else queries)
+        const int old = g_lam_lanes;
+        if (value == 0 || value == 4 || value == 8 || value == 16 || value == 32 || value == 64)
+            g_lam_lanes = value;
+        return old;
+    }
+    if (key == 16) {  // forced Chebyshev iterate count (benchmarking only; bb_nid.hip)
+        const int old = g_nid_force_k;
+        if (value >= 0) nid_set_force_k(std::min(value, 64));
+        return old;
+    }
+    return -1;
 }
 void bb_set_trace_budget(long long bytes) {
     g_trace_budget = bytes > 0 ? (size_t)bytes : (size_t(1) << 30);
@@ -4320,8 +3218,8 @@ void bridge_reg_stable(double *betap, double *lambdap, double *sig2p, double *ta
     const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
                                            alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
                                            ortho);
-    if (stable_dense(c, yp, Xp, *burn, betap, lambdap, sig2p, taup, alphap, runtime,
-                     "Bridge Regression (mix. of normals):") == OUT_INTERRUPTED)
+    if (dense_call(stable_kind(*burn), c, yp, Xp, *burn, {betap, lambdap, sig2p, taup, alphap},
+                   runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 
@@ -4334,190 +3232,14 @@ void bridge_reg_stable_chains(double *betap, double *lambdap, double *sig2p, dou
                               const double *true_alpha, const int *P, const int *N,
                               const int *M, const int *burn, double *runtime,
                               const int *ortho, const int *nchains) {
-    if (*nchains < 1) {  // before a key is taken or an output is touched
-        set_error("bridge_reg_stable_chains: nchains must be at least 1 (got %d)", *nchains);
-        printf("Error: %s\n", g_last_error.c_str());
-        fflush(stdout);
-        return;
-    }
+    if (!nchains_ok("bridge_reg_stable_chains", *nchains)) return;
     const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
                                            alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
                                            ortho, *nchains);
-    if (stable_chains(c, *nchains, yp, Xp, *burn, betap, lambdap, sig2p, taup, alphap,
-                      runtime) == OUT_INTERRUPTED)
+    if (chains_call(stable_kind(*burn), c, *nchains, yp, Xp, *burn,
+                    {betap, lambdap, sig2p, taup, alphap}, runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
-
-}  // extern "C"
-
-namespace {
-
-Outcome stable_csc(const bb_config &c, const double *yp, const int *Xcolptr, const int *Xrowidx,
-                   const double *Xval, int b, double *betap, double *lambdap, double *sig2p,
-                   double *taup, double *alphap, double *runtime) {
-    const int p = c.p, n = c.n;
-    const char *title = "Bridge Regression (mix. of normals):";
-    if (p > n && !c.ortho) {
-        return stable_call(
-            c,
-            [&](const bb_config *cc, int j0, int j1, bb_engine **e) {
-                // the shard's columns: colptr rebased to its first entry
-                std::vector<int> cp(j1 - j0 + 1);
-                for (int j = j0; j <= j1; ++j) cp[j - j0] = Xcolptr[j] - Xcolptr[j0];
-                return bb_engine_create_csc(cc, cp.data(), Xrowidx + Xcolptr[j0],
-                                            Xval + Xcolptr[j0], yp, e);
-            },
-            b, betap, lambdap, sig2p, taup, alphap, runtime, title);
-    }
-    // p <= n or the orthogonal design: the dense paths of bridge_reg_stable (least-squares
-    // start, p x p Cholesky or ortho draw) on the densified X, after the same validation as
-    // the sparse engine's
-    try {
-        csc_validate(n, p, Xcolptr, Xrowidx);
-    } catch (std::exception &ex) {
-        printf("Error: %s\n", ex.what());
-        printf("Aborting Gibbs sampler.\n");
-        fflush(stdout);
-        *runtime = 0.0;
-        return OUT_ERROR;
-    }
-    std::vector<double> Xd((size_t)n * p, 0.0);
-    for (int j = 0; j < p; ++j)
-        for (int q = Xcolptr[j]; q < Xcolptr[j + 1]; ++q) Xd[(size_t)j * n + Xrowidx[q]] = Xval[q];
-    return stable_dense(c, yp, Xd.data(), b, betap, lambdap, sig2p, taup, alphap, runtime, title);
-}
-
-Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, double *betap,
-                   double *lambdap, double *taup, double *alphap, double *runtime) {
-    c.method = 6;
-    for (int i = 0; i < c.n; ++i)
-        if (!(yp[i] == 0.0 || yp[i] == 1.0)) {
-            printf("Error: logistic bridge needs y in {0, 1} (y[%d] = %g)\n", i, yp[i]);
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-            *runtime = 0.0;
-            return OUT_ERROR;
-        }
-    std::vector<double> sig2(c.trace_capacity);
-    return stable_dense(c, yp, Xp, b, betap, lambdap, sig2.data(), taup, alphap, runtime,
-                        "Bridge Regression (logistic, Polya-Gamma mix. of normals):");
-}
-
-// The triangle-mixture driver (BridgeWrapper.cpp:80-204 / :320-432): `burn` sweeps in slot
-// 0, MCMC sample i at t = burn + i.
-Outcome tri_call(const bb_config &c, const double *yp, const double *Xp, int b, double *betap,
-                 double *up, double *omegap, double *shapep, double *sig2p, double *taup,
-                 double *alphap, double *runtime) {
-    const int m = c.trace_capacity;
-    print_banner("Bridge Regression (mix. of triangles):", c, b, m);
-    g_last_interrupted = 0;
-    Outcome o;
-    {
-        Chain ch;
-        if (chain_build(ch, c, 4, [&](const bb_config *cc, int, int, bb_engine **e) {
-                return bb_engine_create(cc, Xp, yp, e);
-            }) != 0) {
-            printf("Error: %s\n", g_last_error.c_str());
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-            *runtime = 0.0;
-            return OUT_ERROR;
-        }
-        g_last_devices = 1;
-        g_last_capacity = ch.cap;
-        o = drive_chain(ch, b, (uint64_t)b, m, b, betap, omegap, sig2p, taup, alphap, runtime, up,
-                        shapep);
-        if (o == OUT_ERROR) {
-            printf("Error: %s\n", g_last_error.c_str());
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-        }
-    }
-    if (g_verbose && o == OUT_OK) printf("Sampling complete: %g sec. for %i iterations.\n", *runtime, m);
-    g_last_interrupted = o == OUT_INTERRUPTED;
-    return o;
-}
-
-// K triangle-mixture chains as one batch on tri_call's schedule (50-sweep blocks, `b` burn-in
-// sweeps, sample i at t = b + i).  The trace budget bounds the batch: each chain's ring gets a
-// K-th; a slot is 4 P-vectors (beta, u, omega, shape) and 3 scalars.
-Outcome tri_chains_batch(const bb_config &c0, int K, const double *yp, const double *Xp, int b,
-                         double *betap, double *up, double *omegap, double *shapep,
-                         double *sig2p, double *taup, double *alphap, double *runtime) {
-    const int m = c0.trace_capacity;
-    *runtime = 0.0;
-    bb_config c = c0;
-    {
-        const size_t per = (size_t)4 * c.p * sizeof(double) + 3 * sizeof(double);
-        size_t cap = g_trace_budget / (size_t)K / per;
-        if (cap < 16) cap = 16;
-        c.trace_capacity = (int)std::min<size_t>(cap, (size_t)(m < 1 ? 1 : m));
-    }
-    bb_chains *raw = nullptr;
-    if (bb_chains_create(&c, K, Xp, yp, &raw) != 0) return OUT_ERROR;
-    std::unique_ptr<bb_chains> ch(raw);
-    g_last_devices = 1;
-    g_last_capacity = ch->cap;
-    ChainsRun run{raw, ch->cap};
-    return drive_schedule(
-        run, 50, b, (uint64_t)b, m, b, runtime,
-        [&](int slot0, int count, int s0) {
-            ch->copy_out(slot0, count, s0, m, betap, omegap, sig2p, taup, alphap, up, shapep);
-            return 0;
-        },
-        [&] {
-            std::vector<uint32_t> f(K, 0u);
-            HIPCHECK(hipMemcpy(f.data(), ch->err, (size_t)K * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost));
-            for (int k = 0; k < K; ++k)
-                if (f[k] & ~4u) {
-                    printf("Error: numerical failure in the device sampler (flags %u) in chain "
-                           "%i\n", f[k], k);
-                    printf("Aborting Gibbs sampler.\n");
-                    fflush(stdout);
-                }
-        });
-}
-
-// bridge_regression_chains: the batch where the fused triangle chain applies, else the K
-// chains one after another through tri_call on streams k1 + c.
-Outcome tri_chains(const bb_config &c, int K, const double *yp, const double *Xp, int b,
-                   double *betap, double *up, double *omegap, double *shapep, double *sig2p,
-                   double *taup, double *alphap, double *runtime) {
-    const size_t m = (size_t)c.trace_capacity, pm = (size_t)c.p * m;
-    *runtime = 0.0;
-    if (chains_refusal(c) == nullptr) {
-        print_banner("Bridge Regression (mix. of triangles):", c, b, (int)m);
-        g_last_interrupted = 0;
-        const Outcome o = tri_chains_batch(c, K, yp, Xp, b, betap, up, omegap, shapep, sig2p,
-                                           taup, alphap, runtime);
-        if (o == OUT_ERROR) {
-            printf("Error: %s\n", g_last_error.c_str());
-            printf("Aborting Gibbs sampler.\n");
-            fflush(stdout);
-        }
-        if (g_verbose && o == OUT_OK)
-            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime,
-                   (int)m, K);
-        g_last_interrupted = o == OUT_INTERRUPTED;
-        return o;
-    }
-    for (int k = 0; k < K; ++k) {
-        bb_config ck = c;
-        ck.stream = c.stream + (uint64_t)k;
-        double rt = 0.0;
-        const Outcome o = tri_call(ck, yp, Xp, b, betap + k * pm, up + k * pm, omegap + k * pm,
-                                   shapep + k * pm, sig2p + k * m, taup + k * m, alphap + k * m,
-                                   &rt);
-        *runtime += rt;
-        if (o == OUT_INTERRUPTED) return o;
-    }
-    return OUT_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 void bridge_reg_stable_csc(double *betap, double *lambdap, double *sig2p, double *taup,
                            double *alphap, const double *yp, const int *Xcolptr,
@@ -4530,7 +3252,7 @@ void bridge_reg_stable_csc(double *betap, double *lambdap, double *sig2p, double
     const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
                                            alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
                                            ortho);
-    if (stable_csc(c, yp, Xcolptr, Xrowidx, Xval, *burn, betap, lambdap, sig2p, taup, alphap,
+    if (stable_csc(c, yp, Xcolptr, Xrowidx, Xval, *burn, {betap, lambdap, sig2p, taup, alphap},
                    runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
@@ -4544,7 +3266,8 @@ void bridge_reg_logit(double *betap, double *lambdap, double *taup, double *alph
     const int no = 0;
     const bb_config c = stable_call_config(&zero, &zero, nu_shape, nu_rate, alpha_a, alpha_b,
                                            &one, true_tau, true_alpha, *P, *N, *M, &no);
-    if (logit_call(c, yp, Xp, *burn, betap, lambdap, taup, alphap, runtime) == OUT_INTERRUPTED)
+    if (logit_call(c, yp, Xp, *burn, {betap, lambdap, nullptr, taup, alphap}, runtime) ==
+        OUT_INTERRUPTED)
         reraise_interrupt();
 }
 
@@ -4557,14 +3280,11 @@ void bridge_regression(double *betap, double *up, double *omegap, double *shapep
                        const int *burn, double *runtime, const int *ortho,
                        const int *betaburn, const int *use_hmc) {
     (void)use_hmc;  // BridgeRegression.cpp:418 forces use_hmc = false
-    const int no = 0;
-    bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
-                                     true_sig2, true_tau, true_alpha, *P, *N, *M, &no);
-    c.method = 4;
-    c.ortho = *ortho != 0;                       // bridge_regression_ortho, :320-432
-    c.betaburn = *betaburn > 0 ? *betaburn : 0;  // BridgeRegression.cpp:407
-    if (tri_call(c, yp, Xp, *burn, betap, up, omegap, shapep, sig2p, taup, alphap, runtime) ==
-        OUT_INTERRUPTED)
+    const bb_config c = tri_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                        alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                        ortho, betaburn);
+    if (dense_call(tri_kind(*burn), c, yp, Xp, *burn,
+                   {betap, omegap, sig2p, taup, alphap, up, shapep}, runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 
@@ -4579,20 +3299,12 @@ void bridge_regression_chains(double *betap, double *up, double *omegap, double 
                               const int *ortho, const int *betaburn, const int *use_hmc,
                               const int *nchains) {
     (void)use_hmc;
-    if (*nchains < 1) {  // before a key is taken or an output is touched
-        set_error("bridge_regression_chains: nchains must be at least 1 (got %d)", *nchains);
-        printf("Error: %s\n", g_last_error.c_str());
-        fflush(stdout);
-        return;
-    }
-    const int no = 0;
-    bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
-                                     true_sig2, true_tau, true_alpha, *P, *N, *M, &no, *nchains);
-    c.method = 4;
-    c.ortho = *ortho != 0;
-    c.betaburn = *betaburn > 0 ? *betaburn : 0;
-    if (tri_chains(c, *nchains, yp, Xp, *burn, betap, up, omegap, shapep, sig2p, taup, alphap,
-                   runtime) == OUT_INTERRUPTED)
+    if (!nchains_ok("bridge_regression_chains", *nchains)) return;
+    const bb_config c = tri_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                        alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                        ortho, betaburn, *nchains);
+    if (chains_call(tri_kind(*burn), c, *nchains, yp, Xp, *burn,
+                    {betap, omegap, sig2p, taup, alphap, up, shapep}, runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 

@@ -1,0 +1,265 @@
+// bb_host.h -- what the host translation units (bb_engine.cpp, bb_prims.cpp) share: the
+// last-error string, HIP / RCCL error checks, the guard every C ABI function runs under, device
+// allocation and a call's scoped scratch, the .C call key and the sparse design.  Internal to
+// the library: everything here has hidden visibility, so nothing becomes a dynamic export.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "bb_kernels.h"
+#include "bb_sparse.h"
+
+#pragma GCC visibility push(hidden)
+namespace bb {
+
+// defined in bb_engine.cpp
+extern thread_local std::string g_last_error;
+extern int g_device;
+extern int g_verbose;
+// Key for one .C call: from R's RNG if present, else (seed, stream++).  A call that runs
+// `count` chains takes the streams k1 .. k1 + count - 1 (one seed drawn under R's RNG).
+void next_call_key(uint64_t *k0, uint64_t *k1, int count = 1);
+
+inline void set_error(const char *fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+}
+
+struct HipError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
+#define HIPCHECK(x)                                                                       \
+    do {                                                                                  \
+        hipError_t e_ = (x);                                                              \
+        if (e_ != hipSuccess) {                                                           \
+            char b_[512];                                                                 \
+            snprintf(b_, sizeof(b_), "HIP error %s at %s:%d: %s", hipGetErrorName(e_),    \
+                     __FILE__, __LINE__, #x);                                             \
+            throw HipError(b_);                                                           \
+        }                                                                                 \
+    } while (0)
+
+#define NCCLCHECK(x)                                                                      \
+    do {                                                                                  \
+        ncclResult_t r_ = (x);                                                            \
+        if (r_ != ncclSuccess) {                                                          \
+            char b_[512];                                                                 \
+            snprintf(b_, sizeof(b_), "RCCL error %s at %s:%d", ncclGetErrorString(r_),    \
+                     __FILE__, __LINE__);                                                 \
+            throw HipError(b_);                                                           \
+        }                                                                                 \
+    } while (0)
+
+// The guard of the C ABI: runs f and turns an exception into bb_last_error() and -1.  f
+// returns nothing (the call then returns 0) or the call's own code (-2 "rejection cap" and
+// friends, having set the error text itself).
+template <class F>
+int guarded(F &&f) {
+    try {
+        if constexpr (std::is_void_v<decltype(f())>) {
+            f();
+            return 0;
+        } else {
+            return f();
+        }
+    } catch (std::exception &ex) {
+        set_error("%s", ex.what());
+        return -1;
+    }
+}
+// ... with `device` made current first
+template <class F>
+int guarded(int device, F &&f) {
+    return guarded([&] {
+        HIPCHECK(hipSetDevice(device));
+        return f();
+    });
+}
+
+inline int round_up(int x, int m) { return ((x + m - 1) / m) * m; }
+
+template <typename T>
+T *dalloc(size_t count, std::vector<void *> &owned) {
+    void *p = nullptr;
+    if (count == 0) count = 1;
+    HIPCHECK(hipMalloc(&p, count * sizeof(T)));
+    HIPCHECK(hipMemset(p, 0, count * sizeof(T)));
+    // the engine's streams are non-blocking: the zero fill must land before their first use
+    HIPCHECK(hipDeviceSynchronize());
+    owned.push_back(p);
+    return (T *)p;
+}
+
+// The device allocations and events of one kernel-level call, released on every way out.
+struct Scratch {
+    std::vector<void *> owned;
+    std::vector<hipEvent_t> events;
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() {
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (void *q : owned) (void)hipFree(q);
+    }
+    template <typename T>
+    T *alloc(size_t count) {
+        return dalloc<T>(count, owned);
+    }
+    hipEvent_t event() {
+        hipEvent_t e;
+        HIPCHECK(hipEventCreate(&e));
+        events.push_back(e);
+        return e;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Sparse design (CSC input): CSC + CSR copies on the device and the Gram pair list
+// (bb_sparse.h).  Built once at setup; X is constant over a chain.
+// ---------------------------------------------------------------------------
+// The canonical dgCMatrix form every CSC entry point requires (colptr[0] = 0,
+// non-decreasing, rows in [0, n), strictly increasing within a column); throws otherwise.
+// Both .C CSC paths (sparse engine and densified dense path) run it, so a malformed matrix
+// is refused the same way whichever path its shape selects.
+inline void csc_validate(int n, int p, const int *cp, const int *ri) {
+    if (cp[0] != 0) throw HipError("CSC: colptr[0] must be 0");
+    for (int j = 0; j < p; ++j) {
+        if (cp[j + 1] < cp[j]) throw HipError("CSC: colptr must be non-decreasing");
+        for (int q = cp[j]; q < cp[j + 1]; ++q) {
+            if (ri[q] < 0 || ri[q] >= n) throw HipError("CSC: row index out of range");
+            if (q > cp[j] && ri[q] <= ri[q - 1])
+                throw HipError("CSC: row indices must be strictly increasing within a "
+                               "column (canonical dgCMatrix form)");
+        }
+    }
+}
+
+struct SparseDesign {
+    int n = 0, n_pad = 0, p = 0;
+    long nnz = 0;
+    size_t pairs = 0;
+    int *colptr = nullptr, *rowidx = nullptr, *rowptr = nullptr, *colidx = nullptr,
+        *cpos = nullptr, *pj = nullptr;
+    double *cval = nullptr, *rval = nullptr, *prod = nullptr;
+    unsigned *estart = nullptr;
+    unsigned short *pidx = nullptr;
+    int max_row = 0;        // largest row nnz
+    bool col_mode = false;  // by-column Gram kernel (max_row <= kSpColMaxRow)
+
+    // Validates the CSC (colptr[0] = 0, non-decreasing, rows in [0, n), strictly increasing
+    // within a column -- R's dgCMatrix is in this canonical form), transposes it on the host
+    // into a CSR with each entry's CSC position, uploads both and builds the pair list.
+    void build(hipStream_t s, int n_, int n_pad_, int p_, const int *cp, const int *ri,
+               const double *cv, std::vector<void *> &owned) {
+        n = n_;
+        n_pad = n_pad_;
+        p = p_;
+        csc_validate(n, p, cp, ri);
+        nnz = cp[p];
+        std::vector<int> rp(n_pad + 1, 0), ci(nnz > 0 ? nnz : 1), pos(nnz > 0 ? nnz : 1);
+        std::vector<double> rv(nnz > 0 ? nnz : 1);
+        for (long q = 0; q < nnz; ++q) ++rp[ri[q] + 1];
+        max_row = 0;
+        for (int r = 0; r < n_pad; ++r) max_row = std::max(max_row, rp[r + 1]);
+        col_mode = max_row <= kSpColMaxRow;
+        for (int r = 0; r < n_pad; ++r) rp[r + 1] += rp[r];
+        std::vector<int> next(rp.begin(), rp.end() - 1);
+        for (int j = 0; j < p; ++j)
+            for (int q = cp[j]; q < cp[j + 1]; ++q) {
+                const int k = next[ri[q]]++;
+                ci[k] = j;
+                rv[k] = cv[q];
+                pos[k] = q;
+            }
+        colptr = dalloc<int>(p + 1, owned);
+        rowidx = dalloc<int>(nnz, owned);
+        cval = dalloc<double>(nnz, owned);
+        rowptr = dalloc<int>(n_pad + 1, owned);
+        colidx = dalloc<int>(nnz, owned);
+        rval = dalloc<double>(nnz, owned);
+        cpos = dalloc<int>(nnz, owned);
+        HIPCHECK(hipMemcpy(colptr, cp, (size_t)(p + 1) * sizeof(int), hipMemcpyHostToDevice));
+        if (nnz > 0) {
+            HIPCHECK(hipMemcpy(rowidx, ri, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(cval, cv, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(colidx, ci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(rval, rv.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(cpos, pos.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+        }
+        HIPCHECK(hipMemcpy(rowptr, rp.data(), (size_t)(n_pad + 1) * sizeof(int),
+                           hipMemcpyHostToDevice));
+        // pair counts per output column, host scan, then the pair list itself
+        unsigned long long *dcnt = nullptr, *dbase = nullptr;
+        HIPCHECK(hipMalloc(&dcnt, (size_t)n_pad * sizeof(unsigned long long)));
+        launch_sp_count(s, rowptr, colidx, cpos, colptr, n_pad, dcnt);
+        std::vector<unsigned long long> cnt(n_pad), base(n_pad);
+        HIPCHECK(hipMemcpyAsync(cnt.data(), dcnt, cnt.size() * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        (void)hipFree(dcnt);
+        unsigned long long tot = 0;
+        for (int c = 0; c < n_pad; ++c) {
+            base[c] = tot;
+            tot += cnt[c];
+        }
+        if (tot > 0xFFFFFF00ull)
+            throw HipError("sparse Gram: more than 2^32 - 1 column pairs (X too dense for the "
+                           "pair-list Gram; use the dense entry point)");
+        pairs = (size_t)tot;
+        size_t fr = 0, total_mem = 0;
+        HIPCHECK(hipMemGetInfo(&fr, &total_mem));
+        const size_t need = pairs * (sizeof(double) + (col_mode ? 2 : sizeof(int))) +
+                            (tri_count(n_pad) + 1) * sizeof(unsigned);
+        if (need + (size_t(1) << 28) > fr) {
+            char b[256];
+            snprintf(b, sizeof(b), "sparse Gram: pair list needs %.2f GB, %.2f GB free", need / 1e9,
+                     fr / 1e9);
+            throw HipError(b);
+        }
+        estart = dalloc<unsigned>(tri_count(n_pad) + 1, owned);
+        prod = dalloc<double>(pairs, owned);
+        if (col_mode)
+            pidx = dalloc<unsigned short>(pairs, owned);
+        else
+            pj = dalloc<int>(pairs, owned);
+        HIPCHECK(hipMalloc(&dbase, (size_t)n_pad * sizeof(unsigned long long)));
+        HIPCHECK(hipMemcpyAsync(dbase, base.data(), base.size() * sizeof(unsigned long long),
+                                hipMemcpyHostToDevice, s));
+        launch_sp_build(s, rowptr, colidx, cpos, rval, colptr, rowidx, cval, n_pad, dbase, estart,
+                        prod, pj, pidx);
+        const unsigned last = (unsigned)tot;
+        HIPCHECK(hipMemcpyAsync(estart + tri_count(n_pad), &last, sizeof(unsigned),
+                                hipMemcpyHostToDevice, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        (void)hipFree(dbase);
+    }
+
+    // tri (packed upper triangle of X diag(D) X', n_pad wide) and xu = X u
+    void gram(hipStream_t s, const double *D, const double *u, double *tri, double *xu,
+              const int *gate = nullptr) const {
+        if (col_mode) {
+            launch_sp_gram_col(s, rowptr, colidx, rval, estart, prod, pidx, D, u, n_pad, max_row,
+                               tri, xu, gate);
+        } else {
+            launch_sp_gram(s, estart, prod, pj, D, n_pad, tri, gate);
+            launch_sp_rows(s, rowptr, colidx, rval, n_pad, u, D, xu, tri, gate);
+        }
+    }
+};
+
+}  // namespace bb
+#pragma GCC visibility pop

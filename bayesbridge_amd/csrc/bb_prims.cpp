@@ -1,0 +1,694 @@
+// bb_prims.cpp -- the kernel-level entry points of include/bayesbridge.h (single draws,
+// Grams, the Cholesky solve and their benchmarks), the bridge EM solver and the reference's
+// small .C sampler entries.  Each call owns its device scratch; none uses the engine.
+#include <cmath>
+#include <cstring>
+
+#include "../../include/bayesbridge.h"
+#include "bb_host.h"
+#include "bb_ozaki.h"
+
+using namespace bb;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// kernel-level entry points
+// ---------------------------------------------------------------------------
+int bb_retstable_batch(double *x, const double *alpha, const double *V0, const double *h, int num,
+                       uint64_t seed, uint64_t stream, uint64_t t, int group) {
+    if (num <= 0) return 0;
+    return guarded(g_device, [&] {
+        Scratch dev;
+        double *da = dev.alloc<double>(num), *dv = dev.alloc<double>(num),
+               *dh = dev.alloc<double>(num), *dx = dev.alloc<double>(num);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        HIPCHECK(hipMemcpy(da, alpha, num * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dv, V0, num * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dh, h, num * sizeof(double), hipMemcpyHostToDevice));
+        if (group <= 0) group = stable_group_for(num);
+        launch_retstable_batch(0, dx, da, dv, dh, num, seed, stream, t, group, de);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(x, dx, num * sizeof(double), hipMemcpyDeviceToHost));
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+        if (f & 4u) {
+            fprintf(stderr, "Problem with parameter.\n");  // retstable.cpp:112-115
+        }
+        const int rc = (int)(f & ~4u) ? -2 : 0;
+        if (rc) set_error("retstable: rejection cap reached (flags %u)", f);
+        return rc;
+    });
+}
+
+int bb_pg_batch(double *omega, const double *psi, int n, uint64_t seed, uint64_t stream,
+                uint64_t t) {
+    if (n <= 0) return 0;
+    return guarded(g_device, [&] {
+        Scratch dev;
+        double *dp = dev.alloc<double>(n), *dw = dev.alloc<double>(n);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        HIPCHECK(hipMemcpy(dp, psi, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        launch_pg(0, dp, n, n, seed, stream, t, dw, de);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(omega, dw, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+        if (f) {
+            set_error("pg: rejection cap reached (flags %u)", f);
+            return -2;
+        }
+        return 0;
+    });
+}
+
+int bb_trunc_batch(int mode, int num, double *x, const double *p0, const double *p1,
+                   const double *p2, const double *p3, uint64_t seed, uint64_t stream) {
+    if (num <= 0) return 0;
+    if (mode < 0 || mode > 5) {
+        set_error("bb_trunc_batch: invalid mode %d", mode);
+        return -1;
+    }
+    static const int nparams[6] = {3, 4, 4, 2, 3, 3};
+    const double *src[4] = {p0, p1, p2, p3};
+    return guarded(g_device, [&] {
+        Scratch dev;
+        double *dp[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int k = 0; k < nparams[mode]; ++k) {
+            dp[k] = dev.alloc<double>(num);
+            HIPCHECK(hipMemcpy(dp[k], src[k], num * sizeof(double), hipMemcpyHostToDevice));
+        }
+        double *dx = dev.alloc<double>(num);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        launch_trunc_batch(0, mode, num, dx, dp[0], dp[1], dp[2], dp[3], seed, stream, de);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(x, dx, num * sizeof(double), hipMemcpyDeviceToHost));
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+        if (f & 256u) {  // BridgeWrapper.cpp:815-822
+            for (int i = 0; i < num; ++i)
+                if (std::isnan(p0[i]) || std::isnan(p1[i]) || std::isnan(p2[i]) ||
+                    std::isinf(p0[i]))
+                    fprintf(stderr, "rtexpon_rate: caught non finite left value: %g; x[i] = %g.\n",
+                            p0[i], (double)NAN);  // printed before the draw overwrites it
+        }
+        const int rc = (f & (64u | 128u)) ? -2 : 0;
+        if (rc) set_error("truncated draw: %s (flags %u)",
+                          (f & 128u) ? "empty truncation interval" : "rejection cap reached", f);
+        return rc;
+    });
+}
+
+int bb_rrtgamma_batch(int num, double *x, const double *shape, const double *rate,
+                      const double *right_t, uint64_t seed, uint64_t stream) {
+    if (num <= 0) return 0;
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const double *src[3] = {shape, rate, right_t};
+        double *dp[3];
+        for (int k = 0; k < 3; ++k) {
+            dp[k] = dev.alloc<double>(num);
+            HIPCHECK(hipMemcpy(dp[k], src[k], num * sizeof(double), hipMemcpyHostToDevice));
+        }
+        double *dx = dev.alloc<double>(num);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        launch_rrtgamma_batch(0, num, dx, dp[0], dp[1], dp[2], seed, stream, de);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(x, dx, num * sizeof(double), hipMemcpyDeviceToHost));
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+        const int rc = f ? -2 : 0;
+        if (rc) set_error("rrtgamma: rejection cap reached (flags %u)", f);
+        return rc;
+    });
+}
+
+int bb_sample_lambda(double *lambda, const double *beta, int p, double alpha, double tau,
+                     uint64_t seed, uint64_t stream, uint64_t t, uint64_t j0, int group) {
+    if (p <= 0) return 0;
+    return guarded(g_device, [&] {
+        Scratch dev;
+        double *db = dev.alloc<double>(p), *dl = dev.alloc<double>(p);
+        DevScalars *dsc = dev.alloc<DevScalars>(1);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        DevScalars s{};
+        s.tau = tau;
+        s.alpha = alpha;
+        HIPCHECK(hipMemcpy(dsc, &s, sizeof(s), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(db, beta, p * sizeof(double), hipMemcpyHostToDevice));
+        if (group <= 0) group = stable_group_for(p);
+        launch_lambda(0, db, p, p, j0, dsc, seed, stream, t, LAMBDA_ONLY, group, dl, nullptr,
+                      nullptr, nullptr, de);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(lambda, dl, p * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int bb_bench_lambda(const double *beta, int p, double alpha, double tau, int group,
+                    int noinline, int reps, double *ms_avg, double *lambda_out) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        double *db = dev.alloc<double>(p), *dl = dev.alloc<double>(p);
+        DevScalars *dsc = dev.alloc<DevScalars>(1);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        DevScalars s{};
+        s.tau = tau;
+        s.alpha = alpha;
+        HIPCHECK(hipMemcpy(dsc, &s, sizeof(s), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(db, beta, p * sizeof(double), hipMemcpyHostToDevice));
+        hipEvent_t e0 = dev.event(), e1 = dev.event();
+        launch_lambda_variant(0, db, p, dsc, 1, 0, 1, group, noinline, dl, de);  // warm
+        HIPCHECK(hipEventRecord(e0, 0));
+        for (int r = 0; r < reps; ++r)
+            launch_lambda_variant(0, db, p, dsc, 1, 0, 2 + r, group, noinline, dl, de);
+        HIPCHECK(hipEventRecord(e1, 0));
+        HIPCHECK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
+        *ms_avg = ms / reps;
+        if (lambda_out)
+            HIPCHECK(hipMemcpy(lambda_out, dl, p * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int bb_bench_chol(int m, int reps, double *ms_factor, double *ms_solve,
+                  unsigned long long *trace) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const int m_pad = round_up(m, kNB);
+        // SPD test matrix: I * m + small symmetric perturbation, built on the host once
+        std::vector<double> h((size_t)m_pad * (m_pad + kNB), 0.0);
+        for (int c = 0; c < m_pad; ++c)
+            for (int r = 0; r <= c; ++r)
+                h[(size_t)r + (size_t)c * m_pad] =
+                    (r == c) ? (double)m_pad : 0.5 * std::sin(0.37 * r + 0.11 * c);
+        for (int r = 0; r < m_pad; ++r) h[(size_t)r + (size_t)m_pad * m_pad] = 1.0;
+        double *src = dev.alloc<double>(h.size()), *dA = dev.alloc<double>(h.size());
+        HIPCHECK(hipMemcpy(src, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        double *Wd = dev.alloc<double>(chol_wd_words(m_pad));
+        unsigned int *fl = dev.alloc<unsigned int>(chol_flag_words(m_pad, 1));
+        double *W = dev.alloc<double>((size_t)m_pad);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        hipEvent_t e0 = dev.event(), e1 = dev.event(), e2 = dev.event();
+        double tf = 0, ts = 0;
+        for (int it = 0; it <= reps; ++it) {
+            HIPCHECK(hipMemcpyAsync(dA, src, h.size() * sizeof(double), hipMemcpyDeviceToDevice, 0));
+            HIPCHECK(hipEventRecord(e0, 0));
+            chol_factor(0, dA, m_pad, m_pad, 1, de, Wd, fl);
+            HIPCHECK(hipEventRecord(e1, 0));
+            chol_bsolve(0, dA, m_pad, m_pad, Wd, dA + (size_t)m_pad * m_pad, W, 1, fl, de);
+            HIPCHECK(hipEventRecord(e2, 0));
+            HIPCHECK(hipEventSynchronize(e2));
+            float a = 0, b = 0;
+            HIPCHECK(hipEventElapsedTime(&a, e0, e1));
+            HIPCHECK(hipEventElapsedTime(&b, e1, e2));
+            if (it > 0) {
+                tf += a;
+                ts += b;
+            }
+        }
+        *ms_factor = tf / reps;
+        *ms_solve = ts / reps;
+        if (trace) {
+            const size_t nts = (size_t)32 * (m_pad / kNB + 1);
+            unsigned long long *dt = dev.alloc<unsigned long long>(nts);
+            HIPCHECK(hipMemset(dt, 0, nts * sizeof(unsigned long long)));
+            HIPCHECK(hipMemcpy(dA, src, h.size() * sizeof(double), hipMemcpyDeviceToDevice));
+            chol_factor(0, dA, m_pad, m_pad, 1, de, Wd, fl, dt);
+            HIPCHECK(hipDeviceSynchronize());
+            HIPCHECK(hipMemcpy(trace, dt, nts * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int bb_gram(double *C, const double *Yh, const double *wh, int n, int k) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const int n_pad = round_up(n, kGramTile);
+        const int k_pad = round_up(k, 256);
+        double *dY = dev.alloc<double>((size_t)n_pad * k_pad);
+        double *dw = dev.alloc<double>(k_pad);
+        HIPCHECK(hipMemcpy2D(dY, (size_t)n_pad * sizeof(double), Yh, (size_t)n * sizeof(double),
+                             (size_t)n * sizeof(double), (size_t)k, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dw, wh, (size_t)k * sizeof(double), hipMemcpyHostToDevice));
+        const int S = gram_splits_for(n_pad, k_pad);
+        const size_t stride = (size_t)n_pad * n_pad;
+        double *sl = dev.alloc<double>(stride * S);
+        double *red = dev.alloc<double>(stride + n_pad);
+        launch_gram(0, dY, n_pad, dw, n_pad, k_pad, S, sl, n_pad, stride);
+        launch_slab_sum(0, sl, S, stride, n_pad, nullptr, 0, red, 1);
+        HIPCHECK(hipGetLastError());
+        std::vector<double> h(tri_count(n_pad));
+        HIPCHECK(hipMemcpy(h.data(), red, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int c = 0; c < n; ++c)
+            for (int r = 0; r < n; ++r)
+                C[(size_t)r + (size_t)c * n] = r <= c ? h[tri_index(r, c)] : h[tri_index(c, r)];
+    });
+}
+
+int bb_gram_ozaki(double *C, const double *Yh, const double *wh, int n, int k) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const int n_pad = round_up(n, kGramTile);
+        const int n_oz = oz_rows(n_pad);
+        const int k_pad = round_up(k, 256);
+        const int nkc = k_pad / kOzKC;
+        double *dY = dev.alloc<double>((size_t)n_pad * k_pad);
+        double *dw = dev.alloc<double>(k_pad);
+        HIPCHECK(hipMemcpy2D(dY, (size_t)n_pad * sizeof(double), Yh, (size_t)n * sizeof(double),
+                             (size_t)n * sizeof(double), (size_t)k, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dw, wh, (size_t)k * sizeof(double), hipMemcpyHostToDevice));
+        const int b = oz_bits_for(k_pad);
+        const int S = oz_splits_for(n_oz, nkc);
+        double *xmax = dev.alloc<double>((size_t)nkc * n_oz);
+        double *rowmax = dev.alloc<double>((size_t)oz_bound_groups(k_pad) * n_oz);
+        double *rscale = dev.alloc<double>(n_oz);
+        int *escale = dev.alloc<int>(n_oz);
+        int8_t *R = dev.alloc<int8_t>(oz_residue_bytes(n_oz, k_pad));
+        int8_t *P = dev.alloc<int8_t>(oz_partial_bytes(n_oz, S));
+        const size_t stride = (size_t)n_pad * n_pad;
+        double *red = dev.alloc<double>(stride + n_pad);
+        launch_oz_xmax(0, dY, n_pad, n_pad, n_oz, k_pad, xmax);
+        launch_oz_scale(0, dw, k_pad, xmax, n_oz, b, rowmax, rscale, escale);
+        launch_oz_residues(0, dY, n_pad, n_pad, n_oz, k_pad, dw, rscale, R);
+        launch_oz_gemm(0, R, n_oz, k_pad, S, P);
+        launch_oz_crt(0, P, S, n_oz, n_pad, escale, nullptr, 0, red);
+        HIPCHECK(hipGetLastError());
+        std::vector<double> h(tri_count(n_pad));
+        HIPCHECK(hipMemcpy(h.data(), red, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int c = 0; c < n; ++c)
+            for (int r = 0; r < n; ++r)
+                C[(size_t)r + (size_t)c * n] = r <= c ? h[tri_index(r, c)] : h[tri_index(c, r)];
+    });
+}
+
+int bb_sparse_gram(double *C, double *xu, const int *colptr, const int *rowidx, const double *val,
+                   const double *D, const double *u, int n, int p) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const int n_pad = round_up(n, kGramTile);
+        SparseDesign sd;
+        sd.build(0, n, n_pad, p, colptr, rowidx, val, dev.owned);
+        double *dD = dev.alloc<double>(p), *du = dev.alloc<double>(p);
+        HIPCHECK(hipMemcpy(dD, D, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+        if (u) HIPCHECK(hipMemcpy(du, u, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+        double *tri = dev.alloc<double>(tri_count(n_pad));
+        double *dxu = dev.alloc<double>(n_pad);
+        sd.gram(0, dD, du, tri, dxu);
+        HIPCHECK(hipGetLastError());
+        std::vector<double> h(tri_count(n_pad));
+        HIPCHECK(hipMemcpy(h.data(), tri, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int c = 0; c < n; ++c)
+            for (int r = 0; r < n; ++r)
+                C[(size_t)r + (size_t)c * n] = r <= c ? h[tri_index(r, c)] : h[tri_index(c, r)];
+        if (xu) HIPCHECK(hipMemcpy(xu, dxu, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int bb_bench_sparse_gram(const int *colptr, const int *rowidx, const double *val, const double *D,
+                         int n, int p, int reps, double *ms_gram, double *ms_rows,
+                         long long *pairs) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const int n_pad = round_up(n, kGramTile);
+        SparseDesign sd;
+        sd.build(0, n, n_pad, p, colptr, rowidx, val, dev.owned);
+        double *dD = dev.alloc<double>(p), *du = dev.alloc<double>(p);
+        HIPCHECK(hipMemcpy(dD, D, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+        double *tri = dev.alloc<double>(tri_count(n_pad));
+        double *dxu = dev.alloc<double>(n_pad);
+        hipEvent_t e0 = dev.event(), e1 = dev.event(), e2 = dev.event();
+        sd.gram(0, dD, du, tri, dxu);  // warm
+        float tg = 0, tr = 0;
+        for (int r = 0; r < reps; ++r) {
+            HIPCHECK(hipEventRecord(e0, 0));
+            if (sd.col_mode)
+                sd.gram(0, dD, du, tri, dxu);
+            else
+                launch_sp_gram(0, sd.estart, sd.prod, sd.pj, dD, n_pad, tri);
+            HIPCHECK(hipEventRecord(e1, 0));
+            if (!sd.col_mode)
+                launch_sp_rows(0, sd.rowptr, sd.colidx, sd.rval, n_pad, du, dD, dxu, tri);
+            HIPCHECK(hipEventRecord(e2, 0));
+            HIPCHECK(hipEventSynchronize(e2));
+            float a = 0, b = 0;
+            HIPCHECK(hipEventElapsedTime(&a, e0, e1));
+            HIPCHECK(hipEventElapsedTime(&b, e1, e2));
+            tg += a;
+            tr += b;
+        }
+        *ms_gram = tg / reps;
+        *ms_rows = tr / reps;
+        if (pairs) *pairs = (long long)sd.pairs;
+    });
+}
+
+int bb_bench_ozaki(int n, int k, int nsplit, int dbg, int reps, double *ms) {
+    return guarded(g_device, [&] {
+        Scratch dev;
+        const int n_oz = oz_rows(round_up(n, kGramTile));
+        const int k_pad = round_up(k, 256);
+        const int S = nsplit > 0 ? nsplit : oz_splits_for(n_oz, k_pad / kOzKC);
+        int8_t *R = dev.alloc<int8_t>(oz_residue_bytes(n_oz, k_pad));
+        int8_t *P = dev.alloc<int8_t>(oz_partial_bytes(n_oz, S));
+        // random residues in [-120, 120]
+        std::vector<int8_t> h(oz_residue_bytes(n_oz, k_pad));
+        uint64_t st = 0x9E3779B97F4A7C15ULL;
+        for (auto &v : h) {
+            st = st * 6364136223846793005ULL + 1442695040888963407ULL;
+            v = (int8_t)((int)((st >> 33) % 241) - 120);
+        }
+        HIPCHECK(hipMemcpy(R, h.data(), h.size(), hipMemcpyHostToDevice));
+        hipEvent_t e0 = dev.event(), e1 = dev.event();
+        // dbg 999: production kernel without K rotation; 1000 + L: with pair lead L / 1000;
+        // 1000000 + 1000 T + L: lead L / 1000 and late shift T / 1000
+        int lead = kOzLeadDefault, late = -1;
+        if (dbg == 999 || (dbg >= 1000 && dbg < 2000)) {
+            lead = dbg == 999 ? -1 : dbg - 1000;
+            dbg = 0;
+        } else if (dbg >= 1000000) {
+            lead = dbg % 1000;
+            late = (dbg / 1000) % 1000;
+            dbg = 0;
+        }
+        launch_oz_gemm(0, R, n_oz, k_pad, S, P, dbg, lead, late);
+        HIPCHECK(hipEventRecord(e0, 0));
+        for (int r = 0; r < reps; ++r) launch_oz_gemm(0, R, n_oz, k_pad, S, P, dbg, lead, late);
+        HIPCHECK(hipEventRecord(e1, 0));
+        HIPCHECK(hipEventSynchronize(e1));
+        float t = 0;
+        HIPCHECK(hipEventElapsedTime(&t, e0, e1));
+        *ms = t / reps;
+    });
+}
+
+int bb_chol_solve(double *x, const double *Ah, const double *bh, int m, int nrhs) {
+    return guarded([&] {
+        if (nrhs < 1 || nrhs > 2) throw HipError("nrhs must be 1 or 2");
+        HIPCHECK(hipSetDevice(g_device));
+        Scratch dev;
+        const int m_pad = round_up(m, kNB);
+        double *dA = dev.alloc<double>((size_t)m_pad * (m_pad + kNB));
+        // identity padding, then the user block and the RHS (forward-solved in place)
+        std::vector<double> h((size_t)m_pad * (m_pad + kNB), 0.0);
+        for (int c = 0; c < m_pad; ++c)
+            for (int r = 0; r <= c; ++r)
+                h[(size_t)r + (size_t)c * m_pad] =
+                    (r < m && c < m) ? Ah[(size_t)r + (size_t)c * m] : (r == c ? 1.0 : 0.0);
+        for (int q = 0; q < nrhs; ++q)
+            for (int r = 0; r < m; ++r) h[(size_t)r + (size_t)(m_pad + q) * m_pad] = bh[r + (size_t)q * m];
+        HIPCHECK(hipMemcpy(dA, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        double *Wd = dev.alloc<double>(chol_wd_words(m_pad));
+        unsigned int *fl = dev.alloc<unsigned int>(chol_flag_words(m_pad, 1));
+        double *W = dev.alloc<double>((size_t)m_pad * nrhs);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        chol_factor(0, dA, m_pad, m_pad, 1, de, Wd, fl);
+        chol_bsolve(0, dA, m_pad, m_pad, Wd, dA + (size_t)m_pad * m_pad, W, nrhs, fl, de);
+        HIPCHECK(hipGetLastError());
+        std::vector<double> hw((size_t)m_pad * nrhs);
+        HIPCHECK(hipMemcpy(hw.data(), W, hw.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int q = 0; q < nrhs; ++q)
+            for (int r = 0; r < m; ++r) x[r + (size_t)q * m] = hw[r + (size_t)q * m_pad];
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+        if (f & 8u) {
+            set_error("matrix is not positive definite");
+            return -3;
+        }
+        return 0;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// Bridge EM (restating BR::EM, Code/C/BridgeRegression.cpp:600-708, with sig = 1 and
+// tau = ratio as the EM wrapper passes them, BridgeWrapper.cpp:57-73).  X'X and X'y are
+// formed once on the device; every maximisation step assembles the masked system on the
+// device (k_em_form), factors it with the persistent Cholesky and back-solves, or runs
+// conjugate gradients (k_em_cg).  The expectation step (lambda_j, the active set, the
+// distance) is an O(p) host loop over the same order as the reference.
+// Returns the number of "solves" (total_iter) or, when every coefficient was dropped, the
+// EM iteration count (the reference's early `return iter`); -1 after an error.
+// ---------------------------------------------------------------------------
+int bb_bridge_em(double *beta_out, const double *yh, const double *Xh, int n, int p, double ratio,
+                 double alpha, double lambda_max, double tol, int max_iter, int use_cg) {
+    std::fill(beta_out, beta_out + p, 0.0);
+    const int ret = guarded(g_device, [&] {
+        Scratch dev;
+        const int n_pad = round_up(n, kGramTile), p_pad = round_up(p, 256);
+        double *dX = dev.alloc<double>((size_t)n_pad * p_pad);
+        double *dy = dev.alloc<double>(n_pad);
+        HIPCHECK(hipMemcpy2D(dX, (size_t)n_pad * sizeof(double), Xh, (size_t)n * sizeof(double),
+                             (size_t)n * sizeof(double), (size_t)p, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dy, yh, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        // G = X'X (transpose, Gram over rows with unit weights), b = X'y
+        double *Xt = dev.alloc<double>((size_t)p_pad * n_pad);
+        launch_transpose(0, dX, n_pad, n_pad, p_pad, Xt, p_pad);
+        double *ones = dev.alloc<double>(n_pad);
+        {
+            std::vector<double> h1(n_pad, 1.0);
+            HIPCHECK(hipMemcpy(ones, h1.data(), n_pad * sizeof(double), hipMemcpyHostToDevice));
+        }
+        const int Sg = gram_splits_for(p_pad, n_pad);
+        const size_t gstride = (size_t)p_pad * p_pad;
+        double *sl = dev.alloc<double>(gstride * Sg);
+        launch_gram(0, Xt, p_pad, ones, p_pad, n_pad, Sg, sl, p_pad, gstride);
+        double *G = dev.alloc<double>(gstride + p_pad);
+        launch_slab_sum(0, sl, Sg, gstride, p_pad, nullptr, 0, G, 0);
+        double *bvec = dev.alloc<double>(p_pad);
+        launch_coldot(0, dX, n_pad, n_pad, dy, p, bvec);
+        double *A = dev.alloc<double>((size_t)p_pad * (p_pad + kNB));
+        double *Wd = dev.alloc<double>(chol_wd_words(p_pad));
+        unsigned int *fl = dev.alloc<unsigned int>(chol_flag_words(p_pad, 1));
+        double *W = dev.alloc<double>(p_pad);
+        double *dlam = dev.alloc<double>(p_pad);
+        int *dmask = dev.alloc<int>(p_pad);
+        double *work = dev.alloc<double>((size_t)3 * p_pad);
+        int *dit = dev.alloc<int>(1);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+
+        std::vector<int> mask(p, 1);
+        std::vector<double> nb(p_pad, 0.0), ob(p, 0.0), lam(p_pad, 0.0);
+        auto upload_mask = [&]() {
+            std::vector<int> m(p_pad, 0);
+            std::copy(mask.begin(), mask.end(), m.begin());
+            HIPCHECK(hipMemcpy(dmask, m.data(), p_pad * sizeof(int), hipMemcpyHostToDevice));
+        };
+        // direct maximisation: A = XX_act (+ c2 diag(lam)), solve by Cholesky (symsolve)
+        auto solve_direct = [&](bool with_lam) {
+            launch_em_form(0, G, p_pad, with_lam ? dlam : nullptr, dmask, bvec, p, p_pad, A,
+                           p_pad, p_pad);
+            HIPCHECK(hipMemset(de, 0, sizeof(uint32_t)));
+            chol_factor(0, A, p_pad, p_pad, 1, de, Wd, fl);
+            chol_bsolve(0, A, p_pad, p_pad, Wd, A + (size_t)p_pad * p_pad, W, 1, fl, de);
+            HIPCHECK(hipGetLastError());
+            uint32_t f = 0;
+            HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+            if (f & 8u) throw HipError("symsolve: matrix is not positive definite");
+            if (f) throw HipError("device solver reported an error");
+            HIPCHECK(hipMemcpy(nb.data(), W, p_pad * sizeof(double), hipMemcpyDeviceToHost));
+        };
+        const double sig = 1.0, tau = ratio;
+        const double c1 = alpha * std::exp((2 - alpha) * (std::log(tau) - std::log(sig)));
+        const double c2 = std::exp(-2 * (std::log(tau) - std::log(sig)));
+        int pa = p;             // active count
+        long total_iter = p;    // the first symsolve
+        upload_mask();
+        solve_direct(false);    // one maximisation step with A = X'X
+        double dist = tol + 1.0;
+        int iter = 0;
+        while (dist > tol && iter < max_iter) {
+            // expectation step over the active coordinates, in order
+            int num = 0;
+            for (int j = 0; j < p; ++j) {
+                if (!mask[j]) continue;
+                const double l = c1 * std::exp((alpha - 2) * std::log(std::fabs(nb[j])));
+                if (l < lambda_max) {
+                    lam[j] = c2 * l;
+                    ob[j] = nb[j];
+                    ++num;
+                } else {
+                    mask[j] = 0;
+                }
+            }
+            if (num < pa) {
+                if (num == 0) return iter;
+                pa = num;
+                upload_mask();
+            }
+            HIPCHECK(hipMemcpy(dlam, lam.data(), p_pad * sizeof(double), hipMemcpyHostToDevice));
+            if (!use_cg) {
+                solve_direct(true);
+                total_iter += pa;
+            } else {
+                // x0 = old beta on the active set (0 elsewhere)
+                std::vector<double> x0(p_pad, 0.0);
+                for (int j = 0; j < p; ++j)
+                    if (mask[j]) x0[j] = ob[j];
+                HIPCHECK(hipMemcpy(W, x0.data(), p_pad * sizeof(double), hipMemcpyHostToDevice));
+                launch_em_form(0, G, p_pad, dlam, dmask, bvec, p, p_pad, A, p_pad, p_pad);
+                launch_em_cg(0, A, p_pad, p_pad, A + (size_t)p_pad * p_pad, W, tol, pa, work,
+                             dit);
+                HIPCHECK(hipGetLastError());
+                int it = 0;
+                HIPCHECK(hipMemcpy(&it, dit, sizeof(int), hipMemcpyDeviceToHost));
+                HIPCHECK(hipMemcpy(nb.data(), W, p_pad * sizeof(double), hipMemcpyDeviceToHost));
+                total_iter += it;
+            }
+            double d2 = 0.0;
+            for (int j = 0; j < p; ++j)
+                if (mask[j]) d2 += (nb[j] - ob[j]) * (nb[j] - ob[j]);
+            dist = std::sqrt(d2);
+            ++iter;
+        }
+        for (int j = 0; j < p; ++j) beta_out[j] = mask[j] ? nb[j] : 0.0;
+        return (int)total_iter;
+    });
+    if (ret < 0) std::fill(beta_out, beta_out + p, 0.0);
+    return ret;
+}
+
+// Batched EM over `count` ratios (trace.beta), direct solves: X'X and X'y once, then one
+// launch in which a workgroup per ratio runs the whole EM -- k_em_batch (system in LDS) for
+// p <= 128, k_em_batch_tiled (system in a global scratch slice per ratio, tiled Cholesky)
+// above, the ratios in chunks whose scratch fits min(free / 2, 16 GiB).
+// beta: count x p (row r = ratio r); solves: count (as bb_bridge_em returns, -1 on a
+// non positive-definite system).  Returns 0, or -1 with bb_last_error().
+int bb_bridge_em_batch(double *beta, int *solves, const double *yh, const double *Xh, int n,
+                       int p, const double *ratios, const double *lambda_max, int count,
+                       double alpha, double tol, int max_iter) {
+    return guarded([&] {
+        if (p < 1) throw HipError("bb_bridge_em_batch: needs p >= 1");
+        if (count < 1) throw HipError("bb_bridge_em_batch: empty ratio grid");
+        HIPCHECK(hipSetDevice(g_device));
+        Scratch dev;
+        const int n_pad = round_up(n, kGramTile), p_pad = round_up(p, 256);
+        double *dX = dev.alloc<double>((size_t)n_pad * p_pad);
+        double *dy = dev.alloc<double>(n_pad);
+        HIPCHECK(hipMemcpy2D(dX, (size_t)n_pad * sizeof(double), Xh, (size_t)n * sizeof(double),
+                             (size_t)n * sizeof(double), (size_t)p, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dy, yh, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        double *Xt = dev.alloc<double>((size_t)p_pad * n_pad);
+        launch_transpose(0, dX, n_pad, n_pad, p_pad, Xt, p_pad);
+        double *ones = dev.alloc<double>(n_pad);
+        {
+            std::vector<double> h1(n_pad, 1.0);
+            HIPCHECK(hipMemcpy(ones, h1.data(), n_pad * sizeof(double), hipMemcpyHostToDevice));
+        }
+        const int Sg = gram_splits_for(p_pad, n_pad);
+        const size_t gstride = (size_t)p_pad * p_pad;
+        double *sl = dev.alloc<double>(gstride * Sg);
+        launch_gram(0, Xt, p_pad, ones, p_pad, n_pad, Sg, sl, p_pad, gstride);
+        double *G = dev.alloc<double>(gstride + p_pad);
+        launch_slab_sum(0, sl, Sg, gstride, p_pad, nullptr, 0, G, 0);
+        double *bvec = dev.alloc<double>(p_pad);
+        launch_coldot(0, dX, n_pad, n_pad, dy, p, bvec);
+        double *dr = dev.alloc<double>(count), *dl = dev.alloc<double>(count);
+        HIPCHECK(hipMemcpy(dr, ratios, count * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(dl, lambda_max, count * sizeof(double), hipMemcpyHostToDevice));
+        double *db = dev.alloc<double>((size_t)count * p);
+        int *ds = dev.alloc<int>(count);
+        if (p <= 128) {
+            launch_em_batch(0, G, p_pad, bvec, p, dr, dl, count, alpha, tol, max_iter, db, ds);
+            HIPCHECK(hipGetLastError());
+        } else {
+            const int pe = round_up(p, em_tile());
+            const size_t per = (size_t)pe * pe * sizeof(double);
+            size_t fr = 0, tot = 0;
+            HIPCHECK(hipMemGetInfo(&fr, &tot));
+            const size_t budget = std::min(fr / 2, (size_t)16 << 30);
+            const int chunk = (int)std::max<size_t>(1, std::min<size_t>(count, budget / per));
+            if (per > fr) throw HipError("bb_bridge_em_batch: p x p system does not fit");
+            double *scr = dev.alloc<double>((size_t)chunk * pe * pe);
+            double *vec = dev.alloc<double>((size_t)chunk * 3 * pe);
+            int *msk = dev.alloc<int>((size_t)chunk * pe);
+            for (int r0 = 0; r0 < count; r0 += chunk) {
+                launch_em_batch_tiled(0, G, p_pad, bvec, p, pe, dr, dl, r0,
+                                      std::min(chunk, count - r0), alpha, tol, max_iter, scr, vec,
+                                      msk, db, ds);
+                HIPCHECK(hipGetLastError());
+            }
+        }
+        HIPCHECK(hipMemcpy(beta, db, (size_t)count * p * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(solves, ds, count * sizeof(int), hipMemcpyDeviceToHost));
+    });
+}
+
+// ---------------------------------------------------------------------------
+// Reference .C entry points
+// ---------------------------------------------------------------------------
+// BridgeWrapper.cpp:738-756: flags NaN / +Inf / -Inf / NA in x[0] and sets x[0] = NA when
+// it is 0 (a marshalling test of R's special values; host only).
+void mytest(int *out, double *x) {
+    const uint64_t na_bits = 0x7FF00000000007A2ull;  // R's NA_REAL
+    uint64_t bits;
+    memcpy(&bits, x, sizeof(bits));
+    out[0] = 0;
+    if (std::isnan(x[0])) out[0] = 1;
+    if (x[0] == HUGE_VAL) out[0] = 2;
+    if (x[0] == -HUGE_VAL) out[0] = 3;
+    if (std::isnan(x[0]) && (uint32_t)bits == 1954u) out[0] = 4;
+    if (x[0] == 0.0) memcpy(x, &na_bits, sizeof(na_bits));
+}
+
+static void trunc_call(int mode, int num, double *x, const double *p0, const double *p1,
+                       const double *p2, const double *p3, const char *name) {
+    uint64_t k0, k1;
+    next_call_key(&k0, &k1);
+    if (bb_trunc_batch(mode, num, x, p0, p1, p2, p3, k0, k1) != 0)
+        fprintf(stderr, "Error: %s: %s\n", name, g_last_error.c_str());
+}
+
+// BridgeWrapper.cpp:843-935 (decl. BridgeWrapper.h:236-242)
+void rtnorm_left(double *x, double *left, double *mu, double *sig, int *num) {
+    trunc_call(0, *num, x, left, mu, sig, nullptr, "rtnorm_left");
+}
+void rtnorm_both(double *x, double *left, double *right, double *mu, double *sig, int *num) {
+    trunc_call(1, *num, x, left, right, mu, sig, "rtnorm_both");
+}
+void rtnorm(double *x, double *left, double *right, double *mu, double *sig, int *num) {
+    trunc_call(2, *num, x, left, right, mu, sig, "rtnorm");
+}
+// BridgeWrapper.cpp:762-830 (decl. BridgeWrapper.h:230-234)
+void rtexpon_rate_left(double *x, double *left, double *rate, int *num) {
+    trunc_call(3, *num, x, left, rate, nullptr, nullptr, "rtexpon_rate_left");
+}
+void rtexpon_rate_both(double *x, double *left, double *right, double *rate, int *num) {
+    trunc_call(4, *num, x, left, right, rate, nullptr, "rtexpon_rate_both");
+}
+void rtexpon_rate(double *x, double *left, double *right, double *rate, int *num) {
+    trunc_call(5, *num, x, left, right, rate, nullptr, "rtexpon_rate");
+}
+
+// BridgeWrapper.cpp:944-962 (decl. BridgeWrapper.h:242); `scale` carries the shape, as
+// rrtgamma (BridgeWrapper.R:482-509) passes it.
+void rrtgamma_rate(double *x, double *scale, double *rate, double *right_t, int *num) {
+    uint64_t k0, k1;
+    next_call_key(&k0, &k1);
+    if (bb_rrtgamma_batch(*num, x, scale, rate, right_t, k0, k1) != 0)
+        fprintf(stderr, "Error: rrtgamma_rate: %s\n", g_last_error.c_str());
+}
+
+void retstable_LD(double *x, double *alpha, double *V0, double *h, int *num) {
+    uint64_t k0, k1;
+    next_call_key(&k0, &k1);
+    int rc = bb_retstable_batch(x, alpha, V0, h, *num, k0, k1, 0, 0);
+    if (rc != 0) fprintf(stderr, "Error: retstable_LD: %s\n", g_last_error.c_str());
+}
+
+// BridgeWrapper.cpp:544-568 (decl. BridgeWrapper.h:166-176); R passes use.cg through
+// as.integer, so it is read as int (BridgeWrapper.R:116-123).  max_iter returns the number
+// of solves; errors print as the reference's EM wrapper does (BridgeWrapper.cpp:64-70).
+void bridge_EM(double *betap, const double *yp, const double *Xp, const double *ratio,
+               const double *alpha, const int *P, const int *N, const double *lambda_max,
+               const double *tol, int *max_iter, const int *use_cg) {
+    if (*use_cg && g_verbose) printf("Using conjugate gradient method.\n");
+    const int it = bb_bridge_em(betap, yp, Xp, *N, *P, *ratio, *alpha, *lambda_max, *tol,
+                                *max_iter, *use_cg);
+    if (it < 0) {
+        printf("Error: %s\n", g_last_error.c_str());
+        printf("Aborting EM.\n");
+    }
+    *max_iter = it;
+}
+
+}  // extern "C"

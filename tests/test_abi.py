@@ -75,6 +75,38 @@ def test_tuning_keys_report_defaults_without_gpu():
         bb.set_tuning(12, old)
 
 
+# key: (default, after set_tuning(key, 1000), after set_tuning(key, 0))
+TUNING_TABLE = {
+    1: (2, 2, 0), 2: (1, 1, 0), 3: (3, 3, 0), 4: (12, 8, 0), 5: (0, 0, 0), 6: (16, 64, 0),
+    7: (3, 3, 0), 8: (1, 2, 0), 9: (0, 1, 0), 10: (1, 1, 0), 11: (1, 1, 0), 12: (1, 1, 0),
+    13: (1, 1, 0), 15: (1, 1, 0), 17: (1, 2, 0), 20: (1, 1, 0), 21: (0, 1, 0),
+}
+
+
+def test_tuning_table_without_gpu():
+    """Every bb_set_tuning key: its default, how it clamps a large value (1000 & 15 = 8 for key
+    4; key 5 takes only its fixed lane counts, so 1000 is ignored) and that 0 is accepted.  A
+    set returns the value it replaces, a negative value only queries.  Key 16 writes a device
+    symbol when set, so it is queried only; keys outside the table answer -1."""
+    old = {key: bb.set_tuning(key, -1) for key in TUNING_TABLE}
+    try:
+        for key, (default, big, zero) in TUNING_TABLE.items():
+            assert old[key] == default, key
+            assert bb.set_tuning(key, 1000) == default, key
+            assert bb.set_tuning(key, -1) == big, key
+            assert bb.set_tuning(key, 0) == big, key
+            assert bb.set_tuning(key, -1) == zero, key
+        assert bb.set_tuning(5, 8) == 0
+        assert bb.set_tuning(5, -1) == 8
+        assert bb.set_tuning(16, -1) == 0
+        for key in (0, 14, 18, 19, 22, 23):
+            assert bb.set_tuning(key, -1) == -1, key
+            assert bb.set_tuning(key, 1) == -1, key
+    finally:
+        for key, v in old.items():
+            bb.set_tuning(key, v)
+
+
 def test_config_struct_layout_matches_header():
     L = bb.library()
     c = bb.bb_config()

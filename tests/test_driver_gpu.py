@@ -87,6 +87,37 @@ def test_interrupt_during_burn_in(gpu_lib):
     assert np.all(np.isfinite(out["beta"][0])) and not out["beta"][1:].any()
 
 
+@pytest.mark.parametrize("fn,burn,keys", [
+    ("bridge_reg_stb_chains", 49, ("beta", "lambda", "sig2", "tau", "alpha")),
+    ("bridge_reg_tri_chains", 50, ("beta", "u", "w", "shape", "sig2", "tau", "alpha")),
+])
+def test_interrupt_in_chain_batch_returns_partial_traces(gpu_lib, fn, burn, keys):
+    """A chain-batch call interrupted at its 3rd poll: burn-in is one 50-sweep block for either
+    method (the stable driver runs burn + 1 sweeps, the triangle driver burn), so the interrupt
+    lands after two blocks of MCMC sweeps.  Every chain returns its first 1 + 2 * 50 samples of
+    every trace bit for bit as the uninterrupted call under the same seed gives them, zeros
+    beyond, and the next call is clean."""
+    bb = gpu_lib
+    X, y, _ = synthetic_problem(12, 3)
+    call = getattr(bb, fn)
+    bb.set_seed(SEED + 7)
+    full = call(y, X, nsamp=160, nchains=3, burn=burn)
+    assert not bb.last_call_info()["interrupted"]
+    bb.set_seed(SEED + 7)
+    bb.debug_interrupt_after(2)
+    part = call(y, X, nsamp=160, nchains=3, burn=burn)
+    assert bb.last_call_info()["interrupted"]
+    done = 1 + 2 * 50
+    for k in keys:
+        assert part[k].shape[:2] == (3, 160), k
+        assert np.array_equal(part[k][:, :done], full[k][:, :done]), k
+        assert not part[k][:, done:].any(), k
+    bb.set_seed(SEED + 7)
+    again = call(y, X, nsamp=160, nchains=3, burn=burn)
+    assert not bb.last_call_info()["interrupted"]
+    _same(full, again, keys)
+
+
 @pytest.mark.parametrize("mode", ["rccl", "ondevice"])
 def test_one_member_group_equals_single_engine(gpu_lib, mode):
     """A one-member shard group (RCCL communicator from ncclCommInitAll, or the on-device

@@ -124,14 +124,19 @@ static const char *kPhaseNames[PH_COUNT] = {"pre", "scalars", "lambda", "pg", "o
                                             "xu", "reduce", "form", "chol", "solve", "beta",
                                             "xb", "alpha", "nid", "eapply", "end"};
 
+// The sampler an engine runs (bb_engine_method exports the values; bb_config::method names the
+// same ones, with AUTO = Cholesky if p <= n, else Woodbury): the p x p Cholesky draw, the dense
+// Woodbury draw, the orthogonal-design draw, the triangle mixture, the sparse Woodbury draw and
+// the logistic (Polya-Gamma) bridge.
+enum Method { AUTO = 0, CHOL = 1, WOODBURY = 2, ORTHO = 3, TRI = 4, SPARSE = 5, LOGIT = 6 };
+
 struct bb_engine {
     bb_config cfg{};
     int n = 0, p = 0, p_loc = 0, n_pad = 0, p_pad = 0;
     // p x p systems (methods 1, 6): factored at round_up(p, 64) inside the p_pad-strided
     // buffers, so a p = 64 design is one block step, not p_pad / 64 = 4
     int chol_m = 0;
-    int method = 0;  // 1 chol, 2 woodbury, 3 ortho, 4 triangle mixture, 5 sparse woodbury,
-                     // 6 logistic (Polya-Gamma)
+    Method method = AUTO;
     int group = 1;
     bool fused = false;  // small p: whole sweeps in one launch (bb_small.hip)
     SparseDesign spd;  // method 5: CSC/CSR design and the Gram pair list
@@ -263,7 +268,13 @@ struct bb_engine {
         return base + (size_t)(slot % cap) * stride;
     }
 
-    bool woodbury() const { return method == 2 || method == 5; }
+    bool woodbury() const { return method == WOODBURY || method == SPARSE; }
+    bool dense() const { return method == WOODBURY; }  // Woodbury over the dense X
+    bool sparse() const { return method == SPARSE; }   // Woodbury over the CSC / CSR X
+    bool ortho() const { return method == ORTHO; }
+    bool tri() const { return method == TRI; }
+    bool logit() const { return method == LOGIT; }
+    bool pxp() const { return method == CHOL || method == LOGIT; }  // factors a p x p system
 
     // the near-identity path: an unsharded Woodbury engine (a one-member RCCL group included:
     // nothing is exchanged) decides on the device against a launch hint; column shards
@@ -284,11 +295,11 @@ struct bb_engine {
     // engine that holds X32 (shards and shard-group members decide the fp64 plan only, so
     // every rank runs the same collectives)
     bool mixed_ok() const {
-        return X32 != nullptr && g_nid_mixed && !sharded() && !group_member && method == 2;
+        return X32 != nullptr && g_nid_mixed && !sharded() && !group_member && dense();
     }
     // the exchanged vectors are single n-vectors on a shard; an unsharded engine in the
     // synchronous mode reads the partials directly
-    bool nid_vec() const { return sharded() || method == 5; }
+    bool nid_vec() const { return sharded() || sparse(); }
 
     // Cost model of the two exact solves, from the round-3/4 measured rates:
     // a Chebyshev solve of K iterates reads X K times (the X u pass and K - 1 products, ~6 TB/s
@@ -300,7 +311,7 @@ struct bb_engine {
     int nid_kmax_model() const {
         double t_pass, t_chol;
         const double steps = n_pad / 64.0;
-        if (method == 5) {
+        if (sparse()) {
             t_pass = 24.0 * (double)spd.nnz / 3.0e12 + 10e-6;
             t_chol = 10.0 * (double)spd.pairs / 4.0e12 + steps * 21e-6 + 60e-6;
         } else {
@@ -356,7 +367,7 @@ struct bb_engine {
     // the Chebyshev solve (kl iterations launched, the device runs mode of them); x is w
     void nid_solve(uint64_t t, int kl) {
         mark(PH_NID);
-        if (method == 5)
+        if (sparse())
             launch_cheb_init(stream, nid_xu, 1, n, n_pad, y, sc, cfg.seed, cfg.stream, t, nid, w,
                              ch_r, ch_d);
         else
@@ -364,13 +375,13 @@ struct bb_engine {
                              cfg.seed, cfg.stream, t, nid, w, ch_r, ch_d);
         for (int j = 1; j < kl; ++j) {
             mark(PH_EAPPLY);
-            if (method == 5)
+            if (sparse())
                 launch_sp_eapply(stream, spd.colptr, spd.rowidx, spd.cval, spd.rowptr, spd.colidx,
                                  spd.rval, p_loc, n_pad, D, ch_d, nid, j, sp_s, ea_part);
             else
                 launch_eapply(stream, X, n_pad, n_pad, p_loc, D, ch_d, nid, j, ea_part);
             mark(PH_NID);
-            launch_cheb_step(stream, ea_part, method == 5 ? 1 : ea_parts, n_pad, sc, nid, j, w,
+            launch_cheb_step(stream, ea_part, sparse() ? 1 : ea_parts, n_pad, sc, nid, j, w,
                              ch_r, ch_d);
         }
     }
@@ -418,6 +429,8 @@ struct bb_engine {
             k2 = (int)((volatile double *)eps_host)[kNidRing + 2];
         }
         nid_k2 = mixed_ok() ? k2 : 0;
+        nid_only = mode > 0;
+        nid_last = mode;
         return mode;
     }
     // Poll the decision's tag word (host2[3]: seq << 16 | mode << 8 | k2, one 64-bit store by
@@ -469,7 +482,7 @@ struct bb_engine {
     // this shard's X u into nid_sum (exchanged: n_pad)
     void nidx_xu() {
         mark(PH_NID);
-        if (method == 5) {
+        if (sparse()) {
             launch_sp_nid_xu(stream, spd.rowptr, spd.colidx, spd.rval, n_pad, u, nid, nid_sum);
         } else {
             if (!xu_fused) launch_nid_xu(stream, X, n_pad, u, p_loc, n_pad, nid, nid_xu);
@@ -503,7 +516,7 @@ struct bb_engine {
     // this shard's E d of step j into nid_sum (exchanged: n_pad)
     void nidx_eapply(int j) {
         mark(PH_EAPPLY);
-        if (method == 5) {
+        if (sparse()) {
             launch_sp_eapply(stream, spd.colptr, spd.rowidx, spd.cval, spd.rowptr, spd.colidx,
                              spd.rval, p_loc, n_pad, D, ch_d, nid, j, sp_s, nid_sum);
         } else {
@@ -519,55 +532,10 @@ struct bb_engine {
         else
             launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d);
     }
-    // a shard's Woodbury sweep between phase b and phase c, through exchange(buf, count)
-    template <class Exchange>
-    void shard_solve(uint64_t t, Exchange exchange) {
-        if (!nid_sync()) {
-            exchange(red2, red2_count());
-            return;
-        }
-        exchange(nid_red, (size_t)kNidRed);
-        nidx_decide_launch();
-        // The start of the Chebyshev solve is enqueued before the host waits for the
-        // decision -- X u, the initial iterate and one product, each returning at once unless
-        // the device decided so -- so the device runs them while the host wakes up (no bubble
-        // on the common near-identity sweep); the rest follows the decision.  A shard's two
-        // exchanges among them run on every rank whatever the decision (the same sequence of
-        // collectives everywhere; on a factor sweep they carry unused vectors).
-        const int spec = g_nid_sync != 2 ? 2 : 0;
-        if (spec) {
-            nidx_xu();
-            if (sharded()) exchange(nid_sum, (size_t)n_pad);
-            nidx_init(t);
-            nidx_eapply(1);
-            if (sharded()) exchange(nid_sum, (size_t)n_pad);
-            nidx_step(1);
-        }
-        const int K = nidx_decide_read();
-        nid_only = K > 0;
-        nid_last = K;
-        if (K > 0) {
-            if (!spec) {
-                nidx_xu();
-                exchange(nid_sum, (size_t)n_pad);
-                nidx_init(t);
-            }
-            for (int j = spec ? spec : 1; j < K; ++j) {
-                nidx_eapply(j);
-                exchange(nid_sum, (size_t)n_pad);
-                nidx_step(j);
-            }
-            if (nid_k2 > 0) nidx_mixed_tail(nid_k2);  // unsharded: exchange() is a no-op
-        } else {
-            wb_gram(nullptr);
-            exchange(red2, red2_count());
-        }
-    }
-
     // X beta of the current beta into the partials k_pre sums next
     void xbeta() {
         xb_stale = false;
-        if (method == 5) {
+        if (sparse()) {
             launch_sp_rows(stream, spd.rowptr, spd.colidx, spd.rval, n_pad, beta, nullptr,
                            xb_part, nullptr);
             nparts = 1;
@@ -577,31 +545,29 @@ struct bb_engine {
         }
     }
 
-    void pre_and_scalars(uint64_t t, int slot, int tau_only) {
+    // the two halves of the tau / sig2 / alpha draw, around the exchange of red1
+    void pre() {
         if (xb_stale) xbeta();
         launch_pre(stream, xb_part, nparts, n_pad, beta, p_loc, sc, red1, nbS);
-        allreduce(red1, (size_t)nbS + n_pad);
+    }
+    void scalars(uint64_t t, int slot, int tau_only) {
         launch_scalars(stream, red1, nbS, y, n, p, sc, hy, cfg.seed, cfg.stream, t,
                        slot_ptr(tr_tau, slot, 1), slot_ptr(tr_sig2, slot, 1),
                        slot_ptr(tr_alpha, slot, 1), tau_only, err);
     }
 
-    // A sweep is three phases separated by the two exchange points of the column-sharded
-    // decomposition: red1 = [S_alpha partials | X beta] and
-    // red2 = [partial Gram | X u].  Single engines and RCCL ranks run them back to back
-    // through allreduce(); a shard group (bb_group_*) interleaves its members' phases.
+    // The phases of a sweep between its exchange points, as sweep_schedule (below) orders them.
     void phase_a(uint64_t t) {
         (void)t;
         if (timing) sweep_marks.emplace_back();
         mark(PH_PRE);
-        if (xb_stale) xbeta();
-        launch_pre(stream, xb_part, nparts, n_pad, beta, p_loc, sc, red1, nbS);
+        pre();
     }
 
     // this shard's (or the whole) Gram X D X' with X u into red2 (packed upper triangle, then
     // the n-vector); gate: the near-identity decision word (its kernels skip on mode != 0)
     void wb_gram(const int *gate) {
-        if (method == 5) {
+        if (sparse()) {
             mark(PH_GRAM);
             spd.gram(stream, D, u, red2, red2 + tri_count(n_pad), gate);
             return;
@@ -632,12 +598,10 @@ struct bb_engine {
 
     void phase_b(uint64_t t, int slot) {
         mark(PH_SCALARS);
-        launch_scalars(stream, red1, nbS, y, n, p, sc, hy, cfg.seed, cfg.stream, t,
-                       slot_ptr(tr_tau, slot, 1), slot_ptr(tr_sig2, slot, 1),
-                       slot_ptr(tr_alpha, slot, 1), 0, err);
+        scalars(t, slot, 0);
         double *trl = slot_ptr(tr_lam, slot, p_loc);
         mark(PH_LAMBDA);
-        if (method == 5 || method == 2) {
+        if (woodbury()) {
             const bool sync = nid_sync();
             const int kl = (!sync && nid_enabled()) ? nid_launch_count() : 0;
             // a sweep that may take the Chebyshev path draws lambda and forms the X u partials
@@ -647,7 +611,7 @@ struct bb_engine {
             // in its own pass)
             xu_fused = 0;
             int folded = 0;
-            if (method == 2 && (sync ? nid_last != 0 : kl > 0)) {
+            if (dense() && (sync ? nid_last != 0 : kl > 0)) {
                 // under the synchronous protocol the split launch also forms the bound sums
                 // (and, unsharded, decides): k_nid_sums / k_nid_reduce are not launched
                 NidFold fold;
@@ -675,7 +639,7 @@ struct bb_engine {
             ++(xu_fused ? n_lambda_xu : n_lambda_alone);
             nid_only = false;
             if (sync) {
-                // a shard: the bound sums now, the path after their exchange (shard_solve)
+                // a shard: the bound sums now, the path after their exchange (solve_schedule)
                 nid_kl = 0;
                 nidx_partials(folded, xu_fused);
                 return;
@@ -684,13 +648,13 @@ struct bb_engine {
             wb_gram(nid_kl ? &nid->mode : nullptr);
             if (nid_kl && !xu_fused) {
                 mark(PH_NID);
-                if (method == 5)
+                if (sparse())
                     launch_sp_nid_xu(stream, spd.rowptr, spd.colidx, spd.rval, n_pad, u, nid,
                                      nid_xu);
                 else
                     launch_nid_xu(stream, X, n_pad, u, p_loc, n_pad, nid, nid_xu);
             }
-        } else if (method == 6) {
+        } else if (logit()) {
             // omega_i ~ PG(1, x_i' beta), x_i' beta from red1 (k_pre's row sums): drawn by
             // trailing workgroups of the speculative lambda launch.  The logistic engine caps
             // p at 16384 (engine create), inside that launch's range (kLamSpecMax).
@@ -715,7 +679,7 @@ struct bb_engine {
                 mark(PH_REDUCE);
                 launch_slab_sum(stream, slabs, S, slab_stride, p_pad, nullptr, 0, Gw, 0);
             }
-        } else if (method == 4) {
+        } else if (tri()) {
             // BridgeWrapper.cpp:166-168: omega, u, then the rtnorm_gibbs beta passes
             mark(PH_BETA);
             launch_tri_update(stream, beta, u, lam, D, p, tVc, tVr, tri_a, tri_d, tri_G, cvec,
@@ -731,10 +695,10 @@ struct bb_engine {
     void phase_c(uint64_t t, int slot, int mcmc_phase) {
         double *trb = slot_ptr(tr_beta, slot, p_loc);
         bool xb_fused = false;
-        if (method == 5 || method == 2) {
+        if (woodbury()) {
             // w = M^-1 (y / sig - v): the Gram + Cholesky path, or (nid_kl > 0 and the device
             // decided so) the Chebyshev solve -- the kernels of the other path return at once
-            // (a shard that took the Chebyshev path solved it in shard_solve: nid_only)
+            // (a shard that took the Chebyshev path solved it in solve_schedule: nid_only)
             const int *gate = nid_kl ? &nid->mode : nullptr;
             if (!nid_only) {
                 mark(PH_FORM);
@@ -748,10 +712,10 @@ struct bb_engine {
             }
             if (nid_kl) nid_solve(t, nid_kl);
         }
-        if (method == 5) {
+        if (sparse()) {
             mark(PH_BETA);
             launch_sp_beta(stream, spd.colptr, spd.rowidx, spd.cval, p_loc, w, u, D, sc, beta, trb);
-        } else if (method == 2) {
+        } else if (dense()) {
             mark(PH_BETA);
             if (beta_xb_supported(n_pad)) {
                 // beta and the X beta partials of the next sweep in one pass over X
@@ -762,12 +726,12 @@ struct bb_engine {
             } else {
                 launch_beta_woodbury(stream, X, n_pad, n_pad, w, u, D, sc, p_loc, beta, trb);
             }
-        } else if (method == 1 || method == 6) {
+        } else if (pxp()) {
             // logistic: A = X'Omega X + diag(lambda / tau^2) (sig2 = 1), c = X'kappa
             mark(PH_FORM);
             const int m = chol_m;  // round_up(p, 64) <= p_pad
-            launch_form_a(stream, method == 6 ? Gw : G, p_pad, lam, sc, cvec, p, m, A, p_pad, m,
-                          method == 6 && cfg.gram_mode == 1);
+            launch_form_a(stream, logit() ? Gw : G, p_pad, lam, sc, cvec, p, m, A, p_pad, m,
+                          logit() && cfg.gram_mode == 1);
             mark(PH_CHOL);
             chol_factor(stream, A, p_pad, m, 1, err, Wd, flags);
             mark(PH_SOLVE);
@@ -775,7 +739,7 @@ struct bb_engine {
             chol_bsolve(stream, A, p_pad, m, Wd, Y2, W2, 2, flags, err);
             mark(PH_BETA);
             launch_beta_chol(stream, W2, m, sc, p, beta, trb);
-        } else if (method == 3) {
+        } else if (ortho()) {
             mark(PH_BETA);
             launch_beta_ortho(stream, gdiag, cvec, lam, sc, p_loc, (uint64_t)cfg.j0, cfg.seed,
                               cfg.stream, t, beta, trb);
@@ -799,9 +763,12 @@ struct bb_engine {
         mark(PH_END);
     }
 
-    // triangle driver: (alpha_a, alpha_b) in both loops (BridgeWrapper.cpp:146,173)
+    // the reference's MH-prior quirk applies: the stable mixture's general driver (Cholesky or
+    // Woodbury draw) passes (alpha_b, alpha_b) in its MCMC loop; the ortho, triangle
+    // (BridgeWrapper.cpp:146,173) and logistic drivers pass (alpha_a, alpha_b) in both loops
+    bool mh_prior_quirk() const { return method == CHOL || woodbury(); }
     double alpha_prior_a(int mcmc_phase) const {
-        return ((method <= 2 || method == 5) && mcmc_phase) ? hy.alpha_b : hy.alpha_a;
+        return (mh_prior_quirk() && mcmc_phase) ? hy.alpha_b : hy.alpha_a;
     }
     // a sharded chain with alpha unknown exchanges the MH sums between phase_c and phase_d
     bool alpha_exchange() const { return !hy.know_alpha && cfg.world > 1; }
@@ -827,6 +794,19 @@ struct bb_engine {
     unsigned int lam_ep = 0;           // its launch epoch (flags are never cleared)
     unsigned long long n_lambda_xu = 0, n_lambda_alone = 0;  // Woodbury lambda launches by kind
 
+    // what a fused chain launch takes from this engine, for its own chain and for the chains
+    // of a batch that shares its design (bb_chains: keys (seed, k1 + chain), its own rings)
+    ChainDesign chain_design() const {
+        return {.X = X, .ldx = n_pad, .n = n, .p = p, .y = y, .G = G, .ldg = p_pad, .cvec = cvec,
+                .gdiag = gdiag, .tVc = tVc, .tVr = tVr, .a = tri_a, .d = tri_d, .Gf = tri_G,
+                .ortho = tri() ? cfg.ortho : ortho(), .betaburn = cfg.betaburn, .hy = hy};
+    }
+    ChainRun chain_run(uint64_t k1, uint64_t t0, int count, int first_slot, int slot_step,
+                       int ring_cap) const {
+        return {.k0 = cfg.seed, .k1 = k1, .t0 = t0, .count = count, .first_slot = first_slot,
+                .slot_step = slot_step, .cap = ring_cap};
+    }
+
     // `count` sweeps from t0 into slots first_slot + k slot_step (mod cap)
     void run(uint64_t t0, int count, int first_slot, int slot_step, int mcmc_phase) {
         if (fused) {
@@ -834,17 +814,14 @@ struct bb_engine {
                 sweep_marks.emplace_back();
                 mark(PH_BETA);
             }
-            if (method == 4)
-                launch_tri_chain(stream, X, n_pad, n, p, y, tVc, tVr, tri_a, tri_d, tri_G, cvec,
-                                 cfg.ortho, beta, u, lam,
-                                 D, sc, hy, cfg.betaburn, cfg.seed, cfg.stream, t0, count,
-                                 first_slot, slot_step, cap, tr_beta, tr_u, tr_lam, tr_shape,
-                                 tr_sig2, tr_tau, tr_alpha, err);
+            const ChainState st{.beta = beta, .lam = lam, .u = u, .shape = D, .sc = sc, .err = err};
+            const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
+                                 .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
+            const ChainRun r = chain_run(cfg.stream, t0, count, first_slot, slot_step, cap);
+            if (tri())
+                launch_tri_chain(stream, chain_design(), st, tr, r);
             else
-                launch_small_chain(stream, X, n_pad, n, p, y, G, p_pad, cvec, gdiag, method == 3,
-                                   beta, lam, sc, hy, cfg.seed, cfg.stream, t0, count,
-                                   first_slot, slot_step, cap, tr_beta, tr_lam, tr_sig2, tr_tau,
-                                   tr_alpha, err);
+                launch_small_chain(stream, chain_design(), st, tr, r);
             if (timing) mark(PH_END);
             xb_stale = true;  // X beta partials refreshed only if a general sweep needs them
             return;
@@ -857,18 +834,7 @@ struct bb_engine {
         }
     }
 
-    void sweep(uint64_t t, int slot, int mcmc_phase) {
-        phase_a(t);
-        allreduce(red1, red1_count());
-        phase_b(t, slot);
-        if (woodbury())
-            shard_solve(t, [this](double *buf, size_t count) { allreduce(buf, count); });
-        phase_c(t, slot, mcmc_phase);
-        if (alpha_exchange()) {
-            allreduce(red3, 2);
-            phase_d(t, slot, mcmc_phase);
-        }
-    }
+    inline void sweep(uint64_t t, int slot, int mcmc_phase);  // sweep_schedule over this engine
 
     uint32_t read_err() {
         uint32_t f = 0;
@@ -878,6 +844,105 @@ struct bb_engine {
     }
     void clear_err() { HIPCHECK(hipMemsetAsync(err, 0, sizeof(uint32_t), stream)); }
 };
+
+// ---------------------------------------------------------------------------
+// The sweep schedule, written once over the engines of `Lanes`, the column shards of one chain
+// that one host thread enqueues (OneEngine below; GroupLanes, the on-device shard group):
+// each(f) runs a stage on every engine, exchange(buf, count) sums a buffer over the shards,
+// first() is the engine whose settings stand for all; spec() is the number of products of the
+// Chebyshev solve enqueued before the host reads the decision, decide() reads the decided K
+// on every engine, phase_c() runs phase c on every engine.
+// ---------------------------------------------------------------------------
+// The draw before burn-in: the tau (tau_only), or the sig2 and tau, of launch_scalars at t = 0
+// into trace slot 0.
+template <class Lanes>
+void preburn_schedule(Lanes &L, int tau_only) {
+    L.each([](bb_engine *e) { e->pre(); });
+    L.exchange(&bb_engine::red1, L.first()->red1_count());
+    L.each([&](bb_engine *e) { e->scalars(0, 0, tau_only); });
+}
+
+// A Woodbury sweep between phase b and phase c: w by the Chebyshev solve (nid_only), or red2
+// for the factor of phase c.
+template <class Lanes>
+void solve_schedule(Lanes &L, uint64_t t) {
+    bb_engine *e0 = L.first();
+    const size_t nv = (size_t)e0->n_pad;
+    if (!e0->nid_sync()) {
+        L.exchange(&bb_engine::red2, e0->red2_count());
+        return;
+    }
+    L.exchange(&bb_engine::nid_red, (size_t)bb_engine::kNidRed);
+    L.each([](bb_engine *e) { e->nidx_decide_launch(); });
+    // The start of the Chebyshev solve is enqueued before the host waits for the decision --
+    // X u, the initial iterate and one product, each returning at once unless the device
+    // decided so -- so the device runs them while the host wakes up (no bubble on the common
+    // near-identity sweep); the rest follows the decision.  A shard's two exchanges among them
+    // run on every rank whatever the decision (the same sequence of collectives everywhere; on
+    // a factor sweep they carry unused vectors); an unsharded engine has nothing to exchange.
+    const int spec = L.spec();
+    if (spec) {
+        L.each([](bb_engine *e) { e->nidx_xu(); });
+        if (e0->sharded()) L.exchange(&bb_engine::nid_sum, nv);
+        L.each([&](bb_engine *e) { e->nidx_init(t); });
+        L.each([](bb_engine *e) { e->nidx_eapply(1); });
+        if (e0->sharded()) L.exchange(&bb_engine::nid_sum, nv);
+        L.each([](bb_engine *e) { e->nidx_step(1); });
+    }
+    const int K = L.decide();
+    if (K > 0) {
+        if (!spec) {
+            L.each([](bb_engine *e) { e->nidx_xu(); });
+            L.exchange(&bb_engine::nid_sum, nv);
+            L.each([&](bb_engine *e) { e->nidx_init(t); });
+        }
+        for (int j = spec ? spec : 1; j < K; ++j) {
+            L.each([&](bb_engine *e) { e->nidx_eapply(j); });
+            L.exchange(&bb_engine::nid_sum, nv);
+            L.each([&](bb_engine *e) { e->nidx_step(j); });
+        }
+        // the mixed plan is an unsharded engine's alone (mixed_ok), so nothing is exchanged
+        if (e0->nid_k2 > 0) L.each([](bb_engine *e) { e->nidx_mixed_tail(e->nid_k2); });
+    } else {
+        L.each([](bb_engine *e) { e->wb_gram(nullptr); });
+        L.exchange(&bb_engine::red2, e0->red2_count());
+    }
+}
+
+// A sweep is three phases separated by the two exchange points of the column-sharded
+// decomposition: red1 = [S_alpha partials | X beta] and, through
+// solve_schedule, red2 = [partial Gram | X u]; alpha unknown adds the exchange of the MH sums.
+template <class Lanes>
+void sweep_schedule(Lanes &L, uint64_t t, int slot, int mcmc_phase) {
+    bb_engine *e0 = L.first();
+    L.each([&](bb_engine *e) { e->phase_a(t); });
+    L.exchange(&bb_engine::red1, e0->red1_count());
+    L.each([&](bb_engine *e) { e->phase_b(t, slot); });
+    if (e0->woodbury()) solve_schedule(L, t);
+    L.phase_c(t, slot, mcmc_phase);
+    if (e0->alpha_exchange()) {
+        L.exchange(&bb_engine::red3, 2);
+        L.each([&](bb_engine *e) { e->phase_d(t, slot, mcmc_phase); });
+    }
+}
+
+// One engine: a single chain, or a rank exchanging through its communicator (allreduce does
+// nothing without one).  The speculative start hides the host's wake-up unless key 8 = 2.
+struct OneEngine {
+    bb_engine *e;
+    bb_engine *first() const { return e; }
+    template <class F>
+    void each(F f) { f(e); }
+    void exchange(double *bb_engine::*buf, size_t count) { e->allreduce(e->*buf, count); }
+    int spec() const { return g_nid_sync != 2 ? 2 : 0; }
+    int decide() { return e->nidx_decide_read(); }
+    void phase_c(uint64_t t, int slot, int mcmc_phase) { e->phase_c(t, slot, mcmc_phase); }
+};
+
+inline void bb_engine::sweep(uint64_t t, int slot, int mcmc_phase) {
+    OneEngine one{this};
+    sweep_schedule(one, t, slot, mcmc_phase);
+}
 
 namespace {
 
@@ -1048,13 +1113,13 @@ void nid_certify_lambda(bb_engine *e) {
     double rho = 0.0;
     for (int it = 0; it < 40; ++it) {
         HIPCHECK(hipMemcpyAsync(e->ch_d, v.data(), n_pad * sizeof(double), hipMemcpyHostToDevice, s));
-        if (e->method == 5)
+        if (e->sparse())
             launch_sp_eapply(s, e->spd.colptr, e->spd.rowidx, e->spd.cval, e->spd.rowptr,
                              e->spd.colidx, e->spd.rval, e->p_loc, n_pad, ones, e->ch_d, gate, 0,
                              e->sp_s, e->ea_part);
         else
             launch_eapply(s, e->X, n_pad, n_pad, e->p_loc, ones, e->ch_d, gate, 0, e->ea_part);
-        launch_part_sum(s, e->ea_part, e->method == 5 ? 1 : e->ea_parts, n_pad, e->ch_r);
+        launch_part_sum(s, e->ea_part, e->sparse() ? 1 : e->ea_parts, n_pad, e->ch_r);
         HIPCHECK(hipMemcpyAsync(w.data(), e->ch_r, n_pad * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHECK(hipStreamSynchronize(s));
         double vw = 0.0, ww = 0.0;
@@ -1069,7 +1134,7 @@ void nid_certify_lambda(bb_engine *e) {
     double lam = 0.0;
     if (rho > 0.0 && std::isfinite(rho)) {
         // the Gram X X' into red2 (packed upper triangle)
-        if (e->method == 5) {
+        if (e->sparse()) {
             e->spd.gram(s, ones, ones, e->red2, e->red2 + tri_count(n_pad));
         } else if (e->cfg.gram_mode == 1) {
             launch_oz_scale(s, ones, p_pad, e->oz_xmax, e->n_oz, e->oz_b, e->oz_rowmax,
@@ -1112,29 +1177,31 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
     e->hy = Hyper{c.sig2_shape, c.sig2_scale, c.nu_shape, c.nu_rate, c.alpha_a, c.alpha_b,
                   c.true_tau > 0, c.true_sig2 > 0, c.true_alpha > 0};
     if (spin) {
-        if (c.ortho || c.method == 1 || c.method == 3 || c.method == 4 || c.method == 6)
+        if (c.ortho || c.method == CHOL || c.method == ORTHO || c.method == TRI ||
+            c.method == LOGIT)
             throw HipError("a CSC design runs the Woodbury (p > n) draw only");
-        e->method = 5;
-    } else if (c.method == 6) {
-        e->method = 6;
+        e->method = SPARSE;
+    } else if (c.method == LOGIT) {
+        e->method = LOGIT;
         e->hy.know_sig2 = 1;  // the PG mixture has unit scale
         // X'Omega X runs over K = n_pad rows: pad to 512 so the Gram can split K 16 ways
         e->n_pad = round_up(c.n, 512);
         if (c.world > 1) throw HipError("the logistic path runs on one device (world == 1)");
         if (c.ortho) throw HipError("the logistic path has no orthogonal-design variant");
         if (c.p > 16384) throw HipError("logistic path limited to p <= 16384");
-    } else if (c.method == 4) e->method = 4;
-    else if (c.ortho) e->method = 3;
-    else if (c.method == 1 || (c.method == 0 && c.p <= c.n)) e->method = 1;
-    else e->method = 2;
+    } else if (c.method == TRI) e->method = TRI;
+    else if (c.ortho) e->method = ORTHO;
+    else if (c.method == CHOL || (c.method == AUTO && c.p <= c.n)) e->method = CHOL;
+    else e->method = WOODBURY;
     // column shards: the p > n Woodbury draws (dense, sparse) and the orthogonal design
     // (per-coefficient draws, p > n); alpha known or unknown (the MH sums are exchanged)
-    if (c.world > 1 && !e->woodbury() && !(e->method == 3 && c.p > c.n))
+    if (c.world > 1 && !e->woodbury() && !(e->ortho() && c.p > c.n))
         throw HipError("column sharding (world > 1) is implemented for the p > n paths only "
                        "(Woodbury, sparse Woodbury, orthogonal design)");
-    if (e->method == 4 && (c.p > c.n || c.p > kTriMaxP))
+    if (e->tri() && (c.p > c.n || c.p > kTriMaxP))
         throw HipError("triangle sampler needs p <= n and p <= 2048");
-    if (e->method == 1 && c.p > 16384) throw HipError("p x p Cholesky path limited to p <= 16384");
+    if (e->method == CHOL && c.p > 16384)
+        throw HipError("p x p Cholesky path limited to p <= 16384");
     if (e->woodbury() && e->n_pad > 8192)
         throw HipError("Woodbury path limited to n <= 8192 in this build");
 
@@ -1160,7 +1227,7 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
     e->err = dalloc<uint32_t>(4, o);
     e->nparts = xv_chunks(p_pad, n_pad);
     e->xb_part = dalloc<double>(
-        (size_t)std::max(e->method == 5 ? 1 : xv_chunks_max(p_pad), beta_xb_parts(c.p_local)) *
+        (size_t)std::max(e->sparse() ? 1 : xv_chunks_max(p_pad), beta_xb_parts(c.p_local)) *
             n_pad,
         o);
     e->nbS = pre_blocks_s(c.p_local);
@@ -1173,7 +1240,7 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
     e->tr_tau = dalloc<double>(e->cap, o);
     e->tr_alpha = dalloc<double>(e->cap, o);
 
-    if (e->method == 2) {
+    if (e->dense()) {
         if (c.gram_mode == 1) {
             e->n_oz = oz_rows(n_pad);
             const int nkc = p_pad / kOzKC;
@@ -1199,9 +1266,9 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
         e->w = dalloc<double>(n_pad, o);
         // near-identity solve (bb_nid.hip); the dense E-apply keeps its rows in registers up
         // to n_pad = 4096
-        if (e->method == 5 || eapply_supported(n_pad)) {
+        if (e->sparse() || eapply_supported(n_pad)) {
             e->cn = dalloc<double>(p_pad, o);
-            if (e->method == 5) {
+            if (e->sparse()) {
                 std::vector<double> h(c.p_local, 0.0);
                 for (int j = 0; j < c.p_local; ++j)
                     for (int q = spin->colptr[j]; q < spin->colptr[j + 1]; ++q)
@@ -1253,7 +1320,7 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
             // element: 400 MB at C3), unless an entry is outside fp32's normal range
             // Only when the plan can be used (key 10 on, a Chebyshev path at all), and never
             // at the price of the engine: a failed allocation keeps the fp64 plan.
-            if (e->method == 2 && c.world == 1 && g_nid_mixed && e->nid_kmax > 0) {
+            if (e->dense() && c.world == 1 && g_nid_mixed && e->nid_kmax > 0) {
                 void *x32 = nullptr;
                 if (hipMalloc(&x32, (size_t)n_pad * p_pad * sizeof(float)) != hipSuccess) {
                     (void)hipGetLastError();  // clear the sticky out-of-memory status
@@ -1278,12 +1345,12 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
         }
     }
     // X'X / X'y when the chol or ortho path needs them, or for the least-squares start.
-    const bool small = c.p <= c.n && c.world == 1 && e->method != 5 && e->method != 6;
+    const bool small = c.p <= c.n && c.world == 1 && !e->sparse() && !e->logit();
     // the Cholesky scratch covers the n x n (Woodbury) and any p x p (chol, LS start) system
     const int m_sys = (e->woodbury() && !small) ? n_pad : (n_pad > p_pad ? n_pad : p_pad);
     e->Wd = dalloc<double>(chol_wd_words(m_sys), o);
     e->flags = dalloc<unsigned int>(chol_flag_words(m_sys, 1), o);
-    if (e->method == 6) {
+    if (e->logit()) {
         // logistic: X' resident (p_pad x n_pad), K-split slabs of X'Omega X, c = X'kappa
         e->Xt = dalloc<double>((size_t)p_pad * n_pad, o);
         launch_transpose(e->stream, e->X, n_pad, n_pad, p_pad, e->Xt, p_pad);
@@ -1314,7 +1381,7 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
         e->A = dalloc<double>((size_t)p_pad * (p_pad + kNB), o);
         e->Y2 = dalloc<double>((size_t)2 * p_pad, o);
         e->W2 = dalloc<double>((size_t)2 * p_pad, o);
-    } else if ((e->method != 2 && e->method != 5) || small) {
+    } else if (!e->woodbury() || small) {
         e->cvec = dalloc<double>(p_pad, o);
         launch_coldot(e->stream, e->X, n_pad, n_pad, e->y, c.p_local, e->cvec);
         e->gdiag = dalloc<double>(p_pad, o);
@@ -1352,11 +1419,11 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
             launch_colnorm2(e->stream, e->X, n_pad, n_pad, c.p_local, e->gdiag);
         }
     }
-    if (e->method == 4) tri_setup(e, Xh);
+    if (e->tri()) tri_setup(e, Xh);
     // small p, one device, alpha known: whole sweeps in one single-workgroup launch
-    e->fused = (e->method == 1 || e->method == 3) && c.p <= kSmallChainMaxP && c.world == 1 &&
-               e->hy.know_alpha && e->cvec && e->gdiag && (e->method == 3 || e->G);
-    if (e->method == 4)  // bb_tri.hip k_tri_chain (general and orthogonal designs)
+    e->fused = (e->method == CHOL || e->ortho()) && c.p <= kSmallChainMaxP && c.world == 1 &&
+               e->hy.know_alpha && e->cvec && e->gdiag && (e->ortho() || e->G);
+    if (e->tri())  // bb_tri.hip k_tri_chain (general and orthogonal designs)
         e->fused = c.p <= kTriChainMaxP && c.world == 1 && e->hy.know_alpha &&
                    (!c.ortho || (e->tri_G && e->cvec));
     if (e->nid) nid_certify_lambda(e);
@@ -1388,17 +1455,17 @@ void engine_init_state_local(bb_engine *e) {
     }
     if (!ls_ok) {
         HIPCHECK(hipMemsetAsync(e->beta, 0, (size_t)e->p_pad * sizeof(double), e->stream));
-        if (g_verbose && c.rank == 0 && e->method != 6) {
+        if (g_verbose && c.rank == 0 && !e->logit()) {
             printf("Warning: cannot calculate least squares estimate; X'X is singular.\n");
             printf("Warning: setting least squares estimate to 0.0.\n");
         }
     }
     DevScalars s{};
     s.alpha = c.true_alpha > 0 ? c.true_alpha : 0.5;
-    s.sig2 = e->method == 6 ? 1.0 : (c.true_sig2 > 0 ? c.true_sig2 : 0.0);
+    s.sig2 = e->logit() ? 1.0 : (c.true_sig2 > 0 ? c.true_sig2 : 0.0);
     s.tau = c.true_tau > 0 ? c.true_tau : 0.0;
     HIPCHECK(hipMemcpyAsync(e->sc, &s, sizeof(s), hipMemcpyHostToDevice, e->stream));
-    if (e->method == 4) {  // BridgeWrapper.cpp:123 u[0].fill(0.5); omega starts at 1.0 (:604)
+    if (e->tri()) {  // BridgeWrapper.cpp:123 u[0].fill(0.5); omega starts at 1.0 (:604)
         std::vector<double> h(e->p_pad, 0.5);
         HIPCHECK(hipMemcpyAsync(e->u, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice,
                                 e->stream));
@@ -1422,11 +1489,12 @@ void engine_init_state_local(bb_engine *e) {
 // and from the state engine_init_state_local left: one rule for a single engine and for every
 // chain of a batch (bb_chains::init_state), so the two cannot drift.
 void engine_preburn_draw(bb_engine *e) {
-    if (e->method == 4 && e->cfg.ortho) {
+    OneEngine one{e};
+    if (e->tri() && e->cfg.ortho) {
         // triangle ortho driver draws sig2 then tau before burn-in (BridgeWrapper.cpp:374-375)
-        if (!e->hy.know_tau || !e->hy.know_sig2) e->pre_and_scalars(0, 0, 0);
-    } else if (e->method != 3 && !e->hy.know_tau) {
-        e->pre_and_scalars(0, 0, 1);  // :262
+        if (!e->hy.know_tau || !e->hy.know_sig2) preburn_schedule(one, 0);
+    } else if (!e->ortho() && !e->hy.know_tau) {
+        preburn_schedule(one, 1);  // :262
     }
 }
 
@@ -1520,14 +1588,14 @@ const char *chains_refusal(const bb_config &c) {
     if (c.n <= 0 || c.p <= 0) return "n and p must be positive";
     if (c.world > 1) return "a chain batch runs on one device (world == 1)";
     if (c.p_local > 0 && c.p_local != c.p) return "a chain batch holds every column (p_local == p)";
-    if (c.method == 4) {  // the triangle mixture: where bb_engine::fused runs k_tri_chain
+    if (c.method == TRI) {  // the triangle mixture: where bb_engine::fused runs k_tri_chain
         static_assert(kTriChainMaxP == 32, "the message below says 32");
         if (c.p > kTriChainMaxP) return "a triangle chain batch needs p <= 32";
         if (c.p > c.n) return "a triangle chain batch needs p <= n";
         if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
         return nullptr;
     }
-    if (c.method != 0 && c.method != 1)
+    if (c.method != AUTO && c.method != CHOL)
         return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or "
                "1) or the triangle mixture (method 4)";
     if (c.p > kSmallChainMaxP) return "a chain batch needs p <= 32";
@@ -1555,11 +1623,11 @@ struct bb_chains {
     uint32_t *err = nullptr;
     double *tr_beta = nullptr, *tr_lam = nullptr, *tr_sig2 = nullptr, *tr_tau = nullptr,
            *tr_alpha = nullptr;
-    // triangle mixture (proto->method == 4): u and shape beside omega (lam)
+    // triangle mixture (proto->tri()): u and shape beside omega (lam)
     double *u = nullptr, *shape = nullptr, *tr_u = nullptr, *tr_shape = nullptr;
     Throttle ahead;
 
-    bool tri() const { return proto->method == 4; }
+    bool tri() const { return proto->tri(); }
     ~bb_chains() {
         if (proto && proto->stream) (void)hipStreamSynchronize(proto->stream);
         for (void *q : owned) (void)hipFree(q);
@@ -1610,19 +1678,14 @@ struct bb_chains {
 
     void run(uint64_t t0, int count, int first_slot, int slot_step) {
         bb_engine *e = proto;
-        if (tri()) {
-            if (launch_tri_chains(e->stream, K, threads, e->X, e->n_pad, e->n, e->p, e->y, e->tVc,
-                                  e->tVr, e->tri_a, e->tri_d, e->tri_G, e->cvec, e->cfg.ortho,
-                                  beta, u, lam, shape, sc, e->hy, e->cfg.betaburn, e->cfg.seed,
-                                  base_stream, t0, count, first_slot, slot_step, cap, tr_beta,
-                                  tr_u, tr_lam, tr_shape, tr_sig2, tr_tau, tr_alpha, err) != 0)
-                throw HipError("no triangle chain-batch instance of that many threads");
-            return;
-        }
-        launch_small_chains(e->stream, K, e->X, e->n_pad, e->n, e->p, e->y, e->G, e->p_pad,
-                            e->cvec, e->gdiag, e->method == 3, beta, lam, sc, e->hy, e->cfg.seed,
-                            base_stream, t0, count, first_slot, slot_step, cap, tr_beta, tr_lam,
-                            tr_sig2, tr_tau, tr_alpha, err, packed);
+        const ChainState st{.beta = beta, .lam = lam, .u = u, .shape = shape, .sc = sc, .err = err};
+        const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
+                             .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
+        const ChainRun r = e->chain_run(base_stream, t0, count, first_slot, slot_step, cap);
+        if (!tri())
+            launch_small_chains(e->stream, K, packed, e->chain_design(), st, tr, r);
+        else if (launch_tri_chains(e->stream, K, threads, e->chain_design(), st, tr, r) != 0)
+            throw HipError("no triangle chain-batch instance of that many threads");
     }
 
     void throttle() { ahead.mark(stream()); }
@@ -1757,12 +1820,12 @@ int bb_engine_create_csc(const bb_config *cfg, const int *colptr, const int *row
 }
 
 long long bb_engine_sparse_pairs(const bb_engine *e) {
-    return e->method == 5 ? (long long)e->spd.pairs : -1;
+    return e->sparse() ? (long long)e->spd.pairs : -1;
 }
 
 int bb_engine_sparse_info(const bb_engine *e, long long *pairs, long long *nnz, int *max_row,
                           int *col_mode) {
-    if (e->method != 5) {
+    if (!e->sparse()) {
         set_error("not a sparse-design engine");
         return -1;
     }
@@ -1874,7 +1937,7 @@ int bb_engine_method(const bb_engine *e) { return e->method; }
 
 int bb_engine_get_omega(bb_engine *e, double *omega) {
     return guarded([&] {
-        if (e->method != 6) throw HipError("not a logistic engine");
+        if (!e->logit()) throw HipError("not a logistic engine");
         HIPCHECK(hipStreamSynchronize(e->stream));
         HIPCHECK(hipMemcpy(omega, e->omega, (size_t)e->n * sizeof(double), hipMemcpyDeviceToHost));
     });
@@ -1882,7 +1945,7 @@ int bb_engine_get_omega(bb_engine *e, double *omega) {
 
 int bb_engine_get_tri_trace(bb_engine *e, int slot0, int count, double *u, double *shape) {
     return guarded([&] {
-        if (e->method != 4) throw HipError("not a triangle-method engine");
+        if (!e->tri()) throw HipError("not a triangle-method engine");
         HIPCHECK(hipStreamSynchronize(e->stream));
         const size_t pl = (size_t)e->p_loc;
         ring_fetch(slot0, count, e->cap, {{u, e->tr_u, pl}, {shape, e->tr_shape, pl}});
@@ -1891,14 +1954,14 @@ int bb_engine_get_tri_trace(bb_engine *e, int slot0, int count, double *u, doubl
 
 int bb_engine_set_tri_state(bb_engine *e, const double *u) {
     return guarded([&] {
-        if (e->method != 4) throw HipError("not a triangle-method engine");
+        if (!e->tri()) throw HipError("not a triangle-method engine");
         HIPCHECK(hipStreamSynchronize(e->stream));
         HIPCHECK(hipMemcpy(e->u, u, (size_t)e->p_loc * sizeof(double), hipMemcpyHostToDevice));
     });
 }
 
 int bb_engine_get_tri_basis(bb_engine *e, double *tV, double *a, double *d) {
-    if (e->method != 4) {
+    if (!e->tri()) {
         set_error("not a triangle-method engine");
         return -1;
     }
@@ -2104,7 +2167,7 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
         c.p_local = c.p;
         c.trace_capacity = 1;  // the shared engine records its own slot 0 only
         if (bb_engine_create(&c, X, y, &b->proto) != 0) throw HipError(g_last_error);
-        if (!b->proto->fused || (b->proto->method == 4) != (c.method == 4))
+        if (!b->proto->fused || b->proto->tri() != (c.method == TRI))
             throw HipError("this design does not run as a fused small chain");
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
@@ -2269,6 +2332,8 @@ unsigned bb_chains_error_flags(bb_chains *b, int chain) {
     }
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------
 // Shard groups: several column-shard engines driven by ONE host thread, interleaving their
 // phases around the two per-sweep exchanges.  Two exchange modes:
@@ -2335,6 +2400,45 @@ struct bb_group {
         for (auto *m : members) HIPCHECK(hipStreamWaitEvent(m->stream, ev, 0));
     }
     void on(bb_engine *m) { HIPCHECK(hipSetDevice(m->cfg.device)); }
+};
+
+// The on-device group as the lanes of sweep_schedule: every stage on each member in turn (on
+// its device), the group's reduce as the exchange, and no speculative start.
+struct GroupLanes {
+    bb_group *g;
+    bb_engine *first() const { return g->members[0]; }
+    template <class F>
+    void each(F f) {
+        for (auto *m : g->members) {
+            g->on(m);
+            f(m);
+        }
+    }
+    void exchange(double *bb_engine::*buf, size_t count) { g->reduce(buf, count); }
+    int spec() const { return 0; }
+    // every member decided from the same reduced sums with the same cap: a member whose
+    // device mode differed would skip both solves (stale w)
+    int decide() {
+        const int K = first()->nidx_decide_read();
+        for (auto *m : g->members)
+            if (m != first() && m->nidx_decide_read() != K)
+                throw HipError("shard group members decided different near-identity paths");
+        return K;
+    }
+    // phase c holds the persistent Cholesky / backward-solve kernels, which need every
+    // workgroup of their grid resident at once: two members' launches on the shared device
+    // must not overlap (two C3-sized factorisations side by side each hold part of the CUs and
+    // wait on tiles owned by workgroups that cannot start), so the members' phase c run one
+    // after another
+    void phase_c(uint64_t t, int slot, int mcmc_phase) {
+        for (size_t i = 0; i < g->members.size(); ++i) {
+            bb_engine *m = g->members[i];
+            g->on(m);
+            if (i > 0) HIPCHECK(hipStreamWaitEvent(m->stream, g->mev[i - 1], 0));
+            m->phase_c(t, slot, mcmc_phase);
+            if (i + 1 < g->members.size()) HIPCHECK(hipEventRecord(g->mev[i], m->stream));
+        }
+    }
 };
 
 namespace {
@@ -2471,89 +2575,10 @@ int bb_group_run(bb_group *g, uint64_t t0, int count, int first_slot, int slot_s
         return 0;
     }
     return guarded([&] {
-        for (int k = 0; k < count; ++k) {
-            const uint64_t t = t0 + (uint64_t)k;
-            const int slot = first_slot < 0 ? -1 : first_slot + k * slot_step;
-            for (auto *m : g->members) {
-                g->on(m);
-                m->phase_a(t);
-            }
-            g->reduce(&bb_engine::red1, g->members[0]->red1_count());
-            for (auto *m : g->members) {
-                g->on(m);
-                m->phase_b(t, slot);
-            }
-            bb_engine *m0 = g->members[0];
-            if (m0->woodbury() && m0->nid_sync()) {
-                // the stages of bb_engine::shard_solve, each over all members, with the
-                // group's reduce as the exchange; every member decides from the same reduced
-                // sums, so member 0's decision is every member's
-                g->reduce(&bb_engine::nid_red, (size_t)bb_engine::kNidRed);
-                for (auto *m : g->members) {
-                    g->on(m);
-                    m->nidx_decide_launch();
-                }
-                const int K = m0->nidx_decide_read();
-                for (auto *m : g->members) {
-                    // every member decided from the same reduced sums with the same cap: a
-                    // member whose device mode differed would skip both solves (stale w)
-                    if (m != m0 && m->nidx_decide_read() != K)
-                        throw HipError("shard group members decided different near-identity "
-                                       "paths");
-                    m->nid_only = K > 0;
-                    m->nid_last = K;
-                }
-                if (K > 0) {
-                    for (auto *m : g->members) {
-                        g->on(m);
-                        m->nidx_xu();
-                    }
-                    g->reduce(&bb_engine::nid_sum, (size_t)m0->n_pad);
-                    for (auto *m : g->members) {
-                        g->on(m);
-                        m->nidx_init(t);
-                    }
-                    for (int j = 1; j < K; ++j) {
-                        for (auto *m : g->members) {
-                            g->on(m);
-                            m->nidx_eapply(j);
-                        }
-                        g->reduce(&bb_engine::nid_sum, (size_t)m0->n_pad);
-                        for (auto *m : g->members) {
-                            g->on(m);
-                            m->nidx_step(j);
-                        }
-                    }
-                } else {
-                    for (auto *m : g->members) {
-                        g->on(m);
-                        m->wb_gram(nullptr);
-                    }
-                    g->reduce(&bb_engine::red2, m0->red2_count());
-                }
-            } else if (m0->woodbury()) {
-                g->reduce(&bb_engine::red2, m0->red2_count());
-            }
-            // phase c holds the persistent Cholesky / backward-solve kernels, which need every
-            // workgroup of their grid resident at once: two members' launches on the shared
-            // device must not overlap (two C3-sized factorisations side by side each hold part
-            // of the CUs and wait on tiles owned by workgroups that cannot start), so the
-            // members' phase c run one after another
-            for (size_t i = 0; i < g->members.size(); ++i) {
-                bb_engine *m = g->members[i];
-                g->on(m);
-                if (i > 0) HIPCHECK(hipStreamWaitEvent(m->stream, g->mev[i - 1], 0));
-                m->phase_c(t, slot, mcmc_phase);
-                if (i + 1 < g->members.size()) HIPCHECK(hipEventRecord(g->mev[i], m->stream));
-            }
-            if (g->members[0]->alpha_exchange()) {
-                g->reduce(&bb_engine::red3, 2);
-                for (auto *m : g->members) {
-                    g->on(m);
-                    m->phase_d(t, slot, mcmc_phase);
-                }
-            }
-        }
+        GroupLanes lanes{g};
+        for (int k = 0; k < count; ++k)
+            sweep_schedule(lanes, t0 + (uint64_t)k, first_slot < 0 ? -1 : first_slot + k * slot_step,
+                           mcmc_phase);
         HIPCHECK(hipGetLastError());
     });
 }
@@ -2579,29 +2604,14 @@ int bb_group_init_state(bb_group *g) {
             g->on(m);
             engine_init_state_local(m);
         }
-        bool draw_tau = g->members[0]->method != 3 && !g->members[0]->hy.know_tau;
-        if (draw_tau) {
-            for (auto *m : g->members) {
-                g->on(m);
-                launch_pre(m->stream, m->xb_part, m->nparts, m->n_pad, m->beta, m->p_loc, m->sc,
-                           m->red1, m->nbS);
-            }
-            g->reduce(&bb_engine::red1, g->members[0]->red1_count());
-            for (auto *m : g->members) {
-                g->on(m);
-                launch_scalars(m->stream, m->red1, m->nbS, m->y, m->n, m->p, m->sc, m->hy,
-                               m->cfg.seed, m->cfg.stream, 0, m->tr_tau, m->tr_sig2,
-                               m->tr_alpha, 1, m->err);
-            }
-        }
+        GroupLanes lanes{g};
+        if (!g->members[0]->ortho() && !g->members[0]->hy.know_tau) preburn_schedule(lanes, 1);
         for (auto *m : g->members) {
             g->on(m);
             HIPCHECK(hipStreamSynchronize(m->stream));
         }
     });
 }
-
-}  // extern "C"
 
 }  // extern "C"
 
@@ -2702,7 +2712,7 @@ int ring_capacity(int m, int p_local, int ntr, int chains = 1) {
 int chain_devices(const bb_config &c, int nvis = -1) {
     if (nvis < 0) nvis = bb_device_count();
     int k = g_max_devices > 0 ? std::min(g_max_devices, nvis) : nvis;
-    if (c.p <= c.n || (c.method != 0 && c.method != 2 && c.method != 3)) return 1;
+    if (c.p <= c.n || (c.method != AUTO && c.method != WOODBURY && c.method != ORTHO)) return 1;
     k = std::min(k, std::max(1, c.p / 4096));
     return std::max(1, k);
 }
@@ -2895,7 +2905,7 @@ void print_banner(const char *title, const bb_config &c, int b, int m) {
     if (!g_verbose) return;  // BridgeWrapper.cpp:235-240 (stable), :112-117 (triangles)
     printf("%s", title);
     if (c.true_alpha > 0) printf(" known alpha=%g", c.true_alpha);
-    if (c.true_sig2 > 0 && c.method != 6) printf(", sig2=%g", c.true_sig2);
+    if (c.true_sig2 > 0 && c.method != LOGIT) printf(", sig2=%g", c.true_sig2);
     if (c.true_tau > 0) printf(", tau=%g", c.true_tau);
     if (c.ortho) printf("\nAssuming orthogonal design matrix!");
     printf("\nBurn-in: %i, Num. Samples: %i\n", b, m);
@@ -3060,7 +3070,7 @@ Outcome stable_csc(const bb_config &c, const double *yp, const int *Xcolptr, con
 
 Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, Traces out,
                    double *runtime) {
-    c.method = 6;
+    c.method = LOGIT;
     for (int i = 0; i < c.n; ++i)
         if (!(yp[i] == 0.0 || yp[i] == 1.0)) {
             print_abort("logistic bridge needs y in {0, 1} (y[%d] = %g)", i, yp[i]);
@@ -3092,7 +3102,7 @@ bb_config tri_call_config(const double *sig2_shape, const double *sig2_scale,
     const int no = 0;
     bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
                                      true_sig2, true_tau, true_alpha, p, n, m, &no, nchains);
-    c.method = 4;
+    c.method = TRI;
     c.ortho = *ortho != 0;                       // bridge_regression_ortho, :320-432
     c.betaburn = *betaburn > 0 ? *betaburn : 0;  // BridgeRegression.cpp:407
     return c;

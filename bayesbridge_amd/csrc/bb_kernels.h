@@ -298,7 +298,7 @@ extern int g_nid_force_k;  // forced Chebyshev iterate count, 0 = certified (key
 void nid_set_force_k(int k);
 extern int g_lam_occ;  // lambda launches at 4 waves per SIMD (bb_set_tuning key 4)
 extern int g_lam_lanes;  // lanes per coefficient of k_lambda_spec, 0 = default (key 5)
-// k_chol_persistent chain variant: 1 (default) or the pipelined 2 / 3, for A/B
+// k_chol_persistent chain variant: 4 (default), or 1 and its pipelined 2 / 3, for A/B
 extern int g_chol_version;
 void chol_factor(hipStream_t s, double *A, int lda, int m_pad, int nrhs_blocks, uint32_t *err,
                  double *Wd, unsigned int *flags, unsigned long long *trace = nullptr, const int *gate = nullptr);
@@ -378,62 +378,70 @@ void launch_pg(hipStream_t s, const double *psi, int n, int n_pad, uint64_t k0, 
                uint64_t t, double *omega, uint32_t *err);
 void launch_kappa(hipStream_t s, const double *y, int n, int n_pad, double *kappa);
 
-// Small-p fused chain (bb_small.hip): `count` whole sweeps (tau, sig2, lambda, beta by the
-// p x p Cholesky draw, or the orthogonal-design draw) in ONE single-workgroup launch, for
-// p <= kSmallChainMaxP and alpha known.  Sweep k uses counter t0 + k and trace slot
-// (first_slot + k slot_step) % cap (first_slot < 0: none).
+// The arguments of the fused chain launchers by role, each filled with designated
+// initialisers (a transposed pair of pointers does not compile silently).
+// What the chains of a launch share, read-only: the design and X'y (cvec), the hyper-parameters,
+// and either the small chain's X'X (G: upper triangle, ld ldg) and its diagonal, or the
+// triangle mixture's basis (tVc, tVr, a, d; ortho != 0: the full Gram Gf) and betaburn.
+struct ChainDesign {
+    const double *X;
+    int ldx, n, p;
+    const double *y;
+    const double *G = nullptr;
+    int ldg = 0;
+    const double *cvec = nullptr, *gdiag = nullptr;
+    const double *tVc = nullptr, *tVr = nullptr, *a = nullptr, *d = nullptr, *Gf = nullptr;
+    int ortho = 0, betaburn = 0;
+    Hyper hy;
+};
+// A chain's state (chain c of a batch: beta + c p, ..., sc[c], err[c]); lam is lambda, or the
+// triangle mixture's omega, whose u and shape the small chain leaves unset.
+struct ChainState {
+    double *beta, *lam, *u = nullptr, *shape = nullptr;
+    DevScalars *sc;
+    uint32_t *err;
+};
+// The trace rings of `cap` slots (chain c of a batch: beta + c cap p, sig2 + c cap, ...).
+struct ChainTraces {
+    double *beta, *lam, *sig2, *tau, *alpha, *u = nullptr, *shape = nullptr;
+};
+// `count` sweeps under the key (k0, k1) (chain c of a batch: (k0, k1 + c)): sweep k uses counter
+// t0 + k and trace slot (first_slot + k slot_step) % cap (first_slot < 0: none).
+struct ChainRun {
+    uint64_t k0, k1, t0;
+    int count, first_slot, slot_step, cap;
+};
+
+// Small-p fused chain (bb_small.hip): whole sweeps (tau, sig2, lambda, beta by the p x p
+// Cholesky draw, or the orthogonal-design draw) in ONE single-workgroup launch, for
+// p <= kSmallChainMaxP and alpha known.
 constexpr int kSmallChainMaxP = 32;
-void launch_small_chain(hipStream_t s, const double *X, int ldx, int n, int p, const double *y,
-                        const double *G, int ldg, const double *cvec, const double *gdiag,
-                        int ortho, double *beta, double *lam, DevScalars *sc, Hyper hy,
-                        uint64_t k0, uint64_t k1, uint64_t t0, int count, int first_slot,
-                        int slot_step, int cap, double *tr_beta, double *tr_lam, double *tr_sig2,
-                        double *tr_tau, double *tr_alpha, uint32_t *err);
+void launch_small_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
+                        const ChainTraces &tr, const ChainRun &r);
 
 // The same sweeps for `nchains` independent chains in one launch, a workgroup per chain
-// (k_small_chains): chain c has beta + c p, lam + c p, sc[c], err[c], the trace rings
-// tr_beta + c cap p (tr_sig2 + c cap, ...) and the key (k0, k1 + c); X, y, G, cvec and gdiag are
-// shared.  small_chains_resident_per_cu: the workgroups the runtime keeps resident on one CU
-// for an n x p design (-1 if the query fails).  packed: the 256-thread instance, two
+// (k_small_chains).  small_chains_resident_per_cu: the workgroups the runtime keeps resident on
+// one CU for an n x p design (-1 if the query fails).  packed: the 256-thread instance, two
 // workgroups per CU (another summation order of rss and S_alpha than the 512-thread one).
-void launch_small_chains(hipStream_t s, int nchains, const double *X, int ldx, int n, int p,
-                         const double *y, const double *G, int ldg, const double *cvec,
-                         const double *gdiag, int ortho, double *beta, double *lam, DevScalars *sc,
-                         Hyper hy, uint64_t k0, uint64_t k1, uint64_t t0, int count,
-                         int first_slot, int slot_step, int cap, double *tr_beta, double *tr_lam,
-                         double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err,
-                         int packed);
+void launch_small_chains(hipStream_t s, int nchains, int packed, const ChainDesign &d,
+                         const ChainState &c, const ChainTraces &tr, const ChainRun &r);
 int small_chains_resident_per_cu(int n, int p, int packed);
 
-// Whole triangle-mixture sweeps (non-orthogonal design, alpha known, p <= kTriChainMaxP) in
-// one single-workgroup launch (bb_tri.hip k_tri_chain): S_alpha / rss, tau and sig2, then
-// omega, u and the rtnorm_gibbs passes of launch_tri_update in one wave, `count` sweeps from
-// t0 with the trace-slot convention of launch_small_chain.
+// Whole triangle-mixture sweeps (alpha known, p <= kTriChainMaxP) in one single-workgroup
+// launch (bb_tri.hip k_tri_chain): S_alpha / rss, tau and sig2, then omega, u and the
+// rtnorm_gibbs passes of launch_tri_update in one wave.
 constexpr int kTriChainMaxP = 32;
-void launch_tri_chain(hipStream_t s, const double *X, int ldx, int n, int p, const double *y,
-                      const double *tVc, const double *tVr, const double *a, const double *d,
-                      const double *Gf, const double *c, int ortho, double *beta, double *u, double *omega, double *shape, DevScalars *sc,
-                      Hyper hy, int betaburn, uint64_t k0, uint64_t k1, uint64_t t0, int count,
-                      int first_slot, int slot_step, int cap, double *tr_beta, double *tr_u,
-                      double *tr_omega, double *tr_shape, double *tr_sig2, double *tr_tau,
-                      double *tr_alpha, uint32_t *err);
+void launch_tri_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
+                      const ChainTraces &tr, const ChainRun &r);
 
 // The same sweeps for `nchains` independent chains in one launch, a workgroup per chain
-// (k_tri_chains): chain c has beta + c p (u, omega, shape alike), sc[c], err[c], the trace
-// rings tr_beta + c cap p (tr_sig2 + c cap, ...) and the key (k0, k1 + c); X, y, the basis (or
-// Gf, c), hy and betaburn are shared.  `threads` names the instance: 512 (the single chain's
-// LDS layout), or 256 or 128, which keep 512 virtual threads and size their LDS by p, so that
-// several chains share a CU; every instance gives the single chain's bits.  Returns -1
-// if there is no such instance.  tri_chains_resident_per_cu: the workgroups of that instance
-// the runtime keeps resident on one CU for an n x p design (-1 if the query fails).
-int launch_tri_chains(hipStream_t s, int nchains, int threads, const double *X, int ldx, int n,
-                      int p, const double *y, const double *tVc, const double *tVr,
-                      const double *a, const double *d, const double *Gf, const double *c,
-                      int ortho, double *beta, double *u, double *omega, double *shape,
-                      DevScalars *sc, Hyper hy, int betaburn, uint64_t k0, uint64_t k1,
-                      uint64_t t0, int count, int first_slot, int slot_step, int cap,
-                      double *tr_beta, double *tr_u, double *tr_omega, double *tr_shape,
-                      double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err);
+// (k_tri_chains).  `threads` names the instance: 512 (the single chain's LDS layout), or 256 or
+// 128, which keep 512 virtual threads and size their LDS by p, so that several chains share a
+// CU; every instance gives the single chain's bits.  Returns -1 if there is no such instance.
+// tri_chains_resident_per_cu: the workgroups of that instance the runtime keeps resident on one
+// CU for an n x p design (-1 if the query fails).
+int launch_tri_chains(hipStream_t s, int nchains, int threads, const ChainDesign &d,
+                      const ChainState &c, const ChainTraces &tr, const ChainRun &r);
 int tri_chains_resident_per_cu(int n, int p, int threads);
 int tri_chains_threads(int n, int p, int nchains, int cus);  // the instance a batch runs
 

@@ -22,8 +22,8 @@ namespace bb {
 namespace {
 
 constexpr int kSmallMaxP = kSmallChainMaxP;
-constexpr size_t kSmallXLds = 112 * 1024;
-constexpr int kSmallPre = 32;  // sweeps of counter-only variates drawn ahead  // X staged in LDS up to this size
+constexpr size_t kSmallXLds = 112 * 1024;  // X staged in LDS up to this size
+constexpr int kSmallPre = 32;  // sweeps of counter-only variates drawn ahead
 
 __device__ __forceinline__ double wave_sum_all(double v) {
 #pragma unroll
@@ -64,9 +64,8 @@ void small_phase_ticks(unsigned long long out[4]) {
     } while (0)
 #endif
 
-// L lanes per coefficient in the lambda draw (stable_spec_draw<L, I>), the p x p system
-// dynamic LDS holds
-// X (n x p, column-major) when it fits, else X is read from HBM each sweep.
+// L lanes per coefficient in the lambda draw (stable_spec_draw<L, I>).  Dynamic LDS holds X
+// (n x p, column-major) when it fits, else X is read from HBM each sweep.
 // small_chain_body is the whole sweep loop of one chain in one workgroup: k_small_chain runs
 // it once, k_small_chains once per workgroup on that chain's state, so the arithmetic exists
 // once.
@@ -337,57 +336,19 @@ __global__ __launch_bounds__(NT, 2) void k_small_chains(
                                tr_tau + ring, tr_alpha + ring, err + c);
 }
 
-// Dynamic LDS above the 64 KB default needs a per-kernel opt-in: done once for every
-// instance (thread-safe static init), with the launch error checked by the caller.
-template <int NT, int L, int I>
-static void small_chain_lds_optin() {
-    static const hipError_t rc = hipFuncSetAttribute(
-        (const void *)k_small_chain<NT, L, I>, hipFuncAttributeMaxDynamicSharedMemorySize,
-        kSmallXLds);
-    (void)rc;
-}
-
-void launch_small_chain(hipStream_t s, const double *X, int ldx, int n, int p, const double *y,
-                        const double *G, int ldg, const double *cvec, const double *gdiag,
-                        int ortho, double *beta, double *lam, DevScalars *sc, Hyper hy,
-                        uint64_t k0, uint64_t k1, uint64_t t0, int count, int first_slot,
-                        int slot_step, int cap, double *tr_beta, double *tr_lam, double *tr_sig2,
-                        double *tr_tau, double *tr_alpha, uint32_t *err) {
-    if (count <= 0) return;
-    const size_t xbytes = (size_t)n * p * sizeof(double);
-    const int x_lds = xbytes <= kSmallXLds;
-    const size_t shm = x_lds ? xbytes : 0;
-    small_chain_lds_optin<512, 64, 16>();
-    small_chain_lds_optin<512, 32, 8>();
-    small_chain_lds_optin<512, 16, 8>();
-    auto go = [&](auto kern, int nt) {
-        kern<<<1, nt, shm, s>>>(X, ldx, n, p, y, G, ldg, cvec, gdiag, ortho, x_lds, beta, lam, sc,
-                                hy, Key{k0, k1}, t0, count, first_slot, slot_step, cap, tr_beta,
-                                tr_lam, tr_sig2, tr_tau, tr_alpha, err);
-    };
-    // lanes per coefficient: as many as the workgroup allows for p coefficients at once
-    static_assert(kSmallMaxP == 32, "instances below cover p <= 32");
-    if (p <= 8) go(k_small_chain<512, 64, 16>, 512);
-    else if (p <= 16) go(k_small_chain<512, 32, 8>, 512);
-    else go(k_small_chain<512, 16, 8>, 512);
-}
-
 namespace {
 
-using SmallChainsKernel = void (*)(const double *, int, int, int, const double *, const double *,
-                                   int, const double *, const double *, int, int, double *,
-                                   double *, DevScalars *, Hyper, Key, uint64_t, int, int, int,
-                                   int, double *, double *, double *, double *, double *,
-                                   uint32_t *);
+using SmallChainsKernel = decltype(&k_small_chains<512, 64, 16>);  // k_small_chain's type too
 
-// the batch instance for p coefficients (the lanes per coefficient of launch_small_chain), its
-// LDS opt-in made once
-SmallChainsKernel small_chains_instance(int p, int packed, int *nt) {
-    static const SmallChainsKernel inst[5] = {k_small_chains<512, 64, 16>,
-                                              k_small_chains<512, 32, 8>,
-                                              k_small_chains<512, 16, 8>,
-                                              k_small_chains<256, 32, 8>,
-                                              k_small_chains<256, 16, 8>};
+// The instance for p coefficients, with as many lanes per coefficient as the workgroup allows
+// for p of them at once: of the single chain (batch == 0), of the batch, or of the packed
+// batch.  Dynamic LDS above the 64 KB default needs a per-kernel opt-in: made once for every
+// instance (thread-safe static init), with the launch error checked by the caller.
+SmallChainsKernel small_chain_instance(int batch, int p, int packed, int *nt) {
+    static const SmallChainsKernel inst[8] = {
+        k_small_chain<512, 64, 16>,  k_small_chain<512, 32, 8>,  k_small_chain<512, 16, 8>,
+        k_small_chains<512, 64, 16>, k_small_chains<512, 32, 8>, k_small_chains<512, 16, 8>,
+        k_small_chains<256, 32, 8>,  k_small_chains<256, 16, 8>};
     static const bool optin = [] {
         for (SmallChainsKernel k : inst)
             (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -396,9 +357,9 @@ SmallChainsKernel small_chains_instance(int p, int packed, int *nt) {
     }();
     (void)optin;
     static_assert(kSmallMaxP == 32, "instances above cover p <= 32");
-    *nt = packed ? 256 : 512;
-    if (packed) return inst[p <= 8 ? 3 : 4];  // p > 16: the lambda draws in two passes
-    return inst[p <= 8 ? 0 : p <= 16 ? 1 : 2];
+    *nt = batch && packed ? 256 : 512;
+    if (batch && packed) return inst[p <= 8 ? 6 : 7];  // p > 16: the lambda draws in two passes
+    return inst[(batch ? 3 : 0) + (p <= 8 ? 0 : p <= 16 ? 1 : 2)];
 }
 
 // dynamic LDS of a launch: X when it fits, and no more than X needs -- a CU holds as many
@@ -409,28 +370,35 @@ size_t small_chain_shm(int n, int p, int *x_lds) {
     return *x_lds ? xbytes : 0;
 }
 
+// `blocks` workgroups of that instance: the structs unpacked into the kernel's arguments
+void small_launch(int batch, int blocks, int packed, hipStream_t s, const ChainDesign &d,
+                  const ChainState &c, const ChainTraces &tr, const ChainRun &r) {
+    if (r.count <= 0 || blocks <= 0) return;
+    int x_lds = 0, nt = 0;
+    const size_t shm = small_chain_shm(d.n, d.p, &x_lds);
+    const SmallChainsKernel kern = small_chain_instance(batch, d.p, packed, &nt);
+    kern<<<blocks, nt, shm, s>>>(
+        d.X, d.ldx, d.n, d.p, d.y, d.G, d.ldg, d.cvec, d.gdiag, d.ortho, x_lds, c.beta, c.lam,
+        c.sc, d.hy, Key{r.k0, r.k1}, r.t0, r.count, r.first_slot, r.slot_step, r.cap, tr.beta,
+        tr.lam, tr.sig2, tr.tau, tr.alpha, c.err);
+}
+
 }  // namespace
 
-void launch_small_chains(hipStream_t s, int nchains, const double *X, int ldx, int n, int p,
-                         const double *y, const double *G, int ldg, const double *cvec,
-                         const double *gdiag, int ortho, double *beta, double *lam, DevScalars *sc,
-                         Hyper hy, uint64_t k0, uint64_t k1, uint64_t t0, int count,
-                         int first_slot, int slot_step, int cap, double *tr_beta, double *tr_lam,
-                         double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err,
-                         int packed) {
-    if (count <= 0 || nchains <= 0) return;
-    int x_lds = 0, nt = 0;
-    const size_t shm = small_chain_shm(n, p, &x_lds);
-    const SmallChainsKernel kern = small_chains_instance(p, packed, &nt);
-    kern<<<nchains, nt, shm, s>>>(
-        X, ldx, n, p, y, G, ldg, cvec, gdiag, ortho, x_lds, beta, lam, sc, hy, Key{k0, k1}, t0,
-        count, first_slot, slot_step, cap, tr_beta, tr_lam, tr_sig2, tr_tau, tr_alpha, err);
+void launch_small_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
+                        const ChainTraces &tr, const ChainRun &r) {
+    small_launch(0, 1, 0, s, d, c, tr, r);
+}
+
+void launch_small_chains(hipStream_t s, int nchains, int packed, const ChainDesign &d,
+                         const ChainState &c, const ChainTraces &tr, const ChainRun &r) {
+    small_launch(1, nchains, packed, s, d, c, tr, r);
 }
 
 int small_chains_resident_per_cu(int n, int p, int packed) {
     int x_lds = 0, blocks = 0, nt = 0;
     const size_t shm = small_chain_shm(n, p, &x_lds);
-    const SmallChainsKernel kern = small_chains_instance(p, packed, &nt);
+    const SmallChainsKernel kern = small_chain_instance(1, p, packed, &nt);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)kern, nt, shm) !=
         hipSuccess) {
         (void)hipGetLastError();

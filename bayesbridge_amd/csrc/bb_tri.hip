@@ -939,25 +939,6 @@ void launch_tri_update(hipStream_t s, double *beta, double *u, double *omega, do
                        tr_omega, tr_shape, err);
 }
 
-void launch_tri_chain(hipStream_t s, const double *X, int ldx, int n, int p, const double *y,
-                      const double *tVc, const double *tVr, const double *a, const double *d,
-                      const double *Gf, const double *c, int ortho, double *beta, double *u, double *omega, double *shape, DevScalars *sc,
-                      Hyper hy, int betaburn, uint64_t k0, uint64_t k1, uint64_t t0, int count,
-                      int first_slot, int slot_step, int cap, double *tr_beta, double *tr_u,
-                      double *tr_omega, double *tr_shape, double *tr_sig2, double *tr_tau,
-                      double *tr_alpha, uint32_t *err) {
-    if (count <= 0 || p < 1 || p > kTriChainMaxP) return;  // the engine checks p at setup
-    const size_t xbytes = (size_t)n * p * sizeof(double);
-    const int x_lds = xbytes <= kTcXLds;
-    static const hipError_t attr = hipFuncSetAttribute(  // one-time opt-in above 64 KB
-        (const void *)k_tri_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTcXLds);
-    (void)attr;
-    k_tri_chain<<<1, kTcNT, x_lds ? xbytes : 0, s>>>(
-        X, ldx, n, p, y, tVc, tVr, a, d, Gf, c, ortho, x_lds, beta, u, omega, shape, sc, hy, betaburn,
-        Key{k0, k1}, t0, count, first_slot, slot_step, cap, tr_beta, tr_u, tr_omega, tr_shape,
-        tr_sig2, tr_tau, tr_alpha, err);
-}
-
 namespace {
 
 using TriChainsKernel = decltype(&k_tri_chains<kTcNT, false>);
@@ -997,25 +978,35 @@ size_t tri_chains_shm(const TriChainsInstance &i, int n, int p, int *x_lds) {
     return (*x_lds ? xbytes : 0) + extra;
 }
 
+// `blocks` workgroups of instance i (k_tri_chain has the kernels' type too): the structs
+// unpacked into its arguments
+void tri_launch(const TriChainsInstance &i, int blocks, hipStream_t s, const ChainDesign &d,
+                const ChainState &c, const ChainTraces &tr, const ChainRun &r) {
+    int x_lds = 0;
+    const size_t shm = tri_chains_shm(i, d.n, d.p, &x_lds);
+    i.kern<<<blocks, i.nt, shm, s>>>(
+        d.X, d.ldx, d.n, d.p, d.y, d.tVc, d.tVr, d.a, d.d, d.Gf, d.cvec, d.ortho, x_lds, c.beta,
+        c.u, c.lam, c.shape, c.sc, d.hy, d.betaburn, Key{r.k0, r.k1}, r.t0, r.count, r.first_slot,
+        r.slot_step, r.cap, tr.beta, tr.u, tr.lam, tr.shape, tr.sig2, tr.tau, tr.alpha, c.err);
+}
+
 }  // namespace
 
-int launch_tri_chains(hipStream_t s, int nchains, int threads, const double *X, int ldx, int n,
-                      int p, const double *y, const double *tVc, const double *tVr,
-                      const double *a, const double *d, const double *Gf, const double *c,
-                      int ortho, double *beta, double *u, double *omega, double *shape,
-                      DevScalars *sc, Hyper hy, int betaburn, uint64_t k0, uint64_t k1,
-                      uint64_t t0, int count, int first_slot, int slot_step, int cap,
-                      double *tr_beta, double *tr_u, double *tr_omega, double *tr_shape,
-                      double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err) {
+void launch_tri_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
+                      const ChainTraces &tr, const ChainRun &r) {
+    if (r.count <= 0 || d.p < 1 || d.p > kTriChainMaxP) return;  // the engine checks p at setup
+    static const hipError_t attr = hipFuncSetAttribute(  // one-time opt-in above 64 KB
+        (const void *)k_tri_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTcXLds);
+    (void)attr;
+    tri_launch({k_tri_chain, kTcNT, false}, 1, s, d, c, tr, r);
+}
+
+int launch_tri_chains(hipStream_t s, int nchains, int threads, const ChainDesign &d,
+                      const ChainState &c, const ChainTraces &tr, const ChainRun &r) {
     const TriChainsInstance *inst = tri_chains_instance(threads);
-    if (!inst || p < 1 || p > kTriChainMaxP) return -1;  // the batch checks both at creation
-    if (count <= 0 || nchains <= 0) return 0;
-    int x_lds = 0;
-    const size_t shm = tri_chains_shm(*inst, n, p, &x_lds);
-    inst->kern<<<nchains, inst->nt, shm, s>>>(
-        X, ldx, n, p, y, tVc, tVr, a, d, Gf, c, ortho, x_lds, beta, u, omega, shape, sc, hy,
-        betaburn, Key{k0, k1}, t0, count, first_slot, slot_step, cap, tr_beta, tr_u, tr_omega,
-        tr_shape, tr_sig2, tr_tau, tr_alpha, err);
+    if (!inst || d.p < 1 || d.p > kTriChainMaxP) return -1;  // the batch checks both at creation
+    if (r.count <= 0 || nchains <= 0) return 0;
+    tri_launch(*inst, nchains, s, d, c, tr, r);
     return 0;
 }
 

@@ -378,7 +378,7 @@ def woodbury_sweep_sharded(Xk, y, beta_k, j0, p, alpha, tau, sig2, t, seed, stre
     delta = normals(n, seed, stream, t, KIND_DELTA)
     if nid_lam is not None:
         # the near-identity decision from the exchanged bound sums (bb_engine.cpp
-        # shard_solve), then either the Chebyshev solve with one exchange of X_k u_k and one
+        # solve_schedule), then either the Chebyshev solve with one exchange of X_k u_k and one
         # per product, or the Gram exchange below
         cn = (Xk * Xk).sum(axis=0)
         eps, K = nid_decide_from(allreduce(nid_shard_partials(D, cn, tau, nid_lam)), tau, sig2,

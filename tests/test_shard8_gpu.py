@@ -5,7 +5,7 @@ sites (VERDICT r4 "next" item 1).
   key; 6250 columns per member -- the shard each rank of an 8-GPU job holds): free-running from
   the reference start every member must report the same path on every sweep, then sweeps are
   teacher-forced against the unsharded engine on the near-identity path and from a fitted
-  state that must take the Gram + Cholesky path (bb_engine.cpp shard_solve and
+  state that must take the Gram + Cholesky path (bb_engine.cpp solve_schedule and
   bb_group_run).
 - bb_set_tuning key 9 makes a world-1 engine with a 1-rank RCCL communicator run the world > 1
   stage sequence (bound-sum exchange, k_nid_decide_from, the exchanged X u and products), so

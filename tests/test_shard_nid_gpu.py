@@ -1,4 +1,4 @@
-"""The column-sharded near-identity solve on the GPU (bb_engine.cpp shard_solve, bb_nid.hip
+"""The column-sharded near-identity solve on the GPU (bb_engine.cpp solve_schedule, bb_nid.hip
 k_nid_partials / k_nid_decide_from).  Shards exchange their bound sums,
 decide the path from the reduced sums (the same bits on every member), then either run the
 Chebyshev iteration with one exchange of X_k u_k and one per product E d, or exchange the

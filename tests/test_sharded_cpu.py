@@ -4,7 +4,7 @@ Each rank holds a column shard of X; per sweep there are two sum all-reduces
 (S_alpha + X beta, then the partial Gram X_k D_k X_k' + X_k u_k).  Variates are indexed by
 the GLOBAL column, so the sharded sweep must reproduce the unsharded one (up to the
 summation order of the Gram).  The HIP engine follows the same decomposition with RCCL
-(bb_engine.cpp: pre_and_scalars / sweep).
+(bb_engine.cpp: preburn_schedule / sweep_schedule).
 """
 import os
 import socket

@@ -83,9 +83,14 @@ int main(int argc, char **argv) {
         unsigned long long ph[4];
         bb::small_phase_ticks(ph);  // zero
         CK(hipEventRecord(e0));
-        bb::launch_small_chain(nullptr, dX, n, n, p, dy, dG, p, dc, dgd, ortho, db, dl, dsc, hy,
-                               11, 22, 1 + (uint64_t)rep * count, count, 0, 1, count, tb, tl, ts,
-                               tt, ta, err);
+        bb::launch_small_chain(
+            nullptr,
+            {.X = dX, .ldx = n, .n = n, .p = p, .y = dy, .G = dG, .ldg = p, .cvec = dc,
+             .gdiag = dgd, .ortho = ortho, .hy = hy},
+            {.beta = db, .lam = dl, .sc = dsc, .err = err},
+            {.beta = tb, .lam = tl, .sig2 = ts, .tau = tt, .alpha = ta},
+            {.k0 = 11, .k1 = 22, .t0 = 1 + (uint64_t)rep * count, .count = count, .first_slot = 0,
+             .slot_step = 1, .cap = count});
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms = 0;

@@ -25,7 +25,8 @@ from . import _build
 __all__ = ["bridge_reg_stb", "bridge_reg", "retstable_ld", "set_seed", "get_rng_state",
            "set_rng_state", "Engine", "EngineConfig", "library", "device_count",
            "sample_lambda", "retstable_batch", "gram", "chol_solve", "bridge_reg_stb_chains",
-           "bridge_reg_tri_chains", "ChainBatch", "compute_units"]
+           "bridge_reg_tri_chains", "ChainBatch", "compute_units",
+           "bridge_reg_stb_chains_summary", "bridge_reg_tri_chains_summary", "trace_summary"]
 
 _lib: Optional[ctypes.CDLL] = None
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -73,7 +74,9 @@ EXPORTED_SYMBOLS = [
     "bb_chains_sync", "bb_chains_get_trace", "bb_chains_get_state", "bb_chains_set_state",
     "bb_chains_error_flags", "bridge_regression_chains", "bb_chains_get_tri_trace",
     "bb_chains_set_tri_state", "bb_chains_get_tri_basis", "bb_chains_threads",
-    "bb_chains_set_threads", "bb_compute_units",
+    "bb_chains_set_threads", "bb_compute_units", "bridge_reg_stable_chains_summary",
+    "bridge_regression_chains_summary", "bb_chains_summary_reset", "bb_chains_summary_add",
+    "bb_chains_summary_get", "bb_trace_summary",
 ]
 
 
@@ -201,6 +204,15 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bridge_regression_chains.argtypes = ([_dp] * 9 + [_dp] * 9 + [_ip] * 4 + [_dp] +
                                            [_ip] * 4)
     L.bb_chains_get_tri_trace.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int, _dp, _dp]
+    L.bridge_reg_stable_chains_summary.argtypes = ([_dp] * 5 + [_ip, _ip] + [_dp] * 2 +
+                                                   [_dp] * 9 + [_ip] * 4 + [_dp, _ip, _ip])
+    L.bridge_regression_chains_summary.argtypes = ([_dp] * 5 + [_ip, _ip] + [_dp] * 2 +
+                                                   [_dp] * 9 + [_ip] * 4 + [_dp] + [_ip] * 4)
+    L.bb_chains_summary_reset.argtypes = [c.c_void_p, c.c_int, c.c_int]
+    L.bb_chains_summary_add.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_int]
+    L.bb_chains_summary_get.argtypes = [c.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip]
+    L.bb_trace_summary.argtypes = [_dp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, _dp, _dp,
+                                   _dp, _dp, _dp]
     L.bb_chains_set_tri_state.argtypes = [c.c_void_p, c.c_int, _dp]
     L.bb_chains_get_tri_basis.argtypes = [c.c_void_p, _dp, _dp, _dp]
     L.bb_chains_threads.argtypes = [c.c_void_p]
@@ -572,6 +584,125 @@ def bridge_reg_tri_chains(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0, sig2_
                                ctypes.byref(rt), i(1 if ortho else 0), i(betaburn), i(0), i(K))
     out.update(sig2=sig2, tau=tau, alpha=alph, runtime=rt.value)
     return out
+
+
+SUMMARY_MAX_LAG = 63
+
+
+def _summary_maxlag(nsamp: int, maxlag) -> int:
+    """maxlag=None: coda's default autoregressive order, at most the kernel's 63 lags."""
+    from .diagnostics import default_maxlag
+
+    return min(SUMMARY_MAX_LAG, default_maxlag(int(nsamp))) if maxlag is None else int(maxlag)
+
+
+def _summary_buffers(K: int, Q: int, L: int):
+    """The caller-allocated outputs of a summary call: Q x K (and so on) column-major is
+    (K, Q[, ...]) in C order.  NaN until written."""
+    L = min(max(L, 0), SUMMARY_MAX_LAG)  # a refused maxlag writes nothing
+    return {"mean": np.full((K, Q), np.nan), "var": np.full((K, Q), np.nan),
+            "acov": np.full((K, Q, L + 1), np.nan), "hmean": np.full((K, Q, 2), np.nan),
+            "hvar": np.full((K, Q, 2), np.nan), "flags": np.zeros(K, dtype=np.int32)}
+
+
+def _summary_result(raw, P: int, nsamp: int, maxlag: int, runtime: float):
+    """The return value of the summary calls: the raw arrays, names, flags, runtime and the
+    sum_stat_chains keys for the coefficients (diagnostics.sum_stat_from_summary)."""
+    from .diagnostics import sum_stat_from_summary
+
+    out = {"chain_mean": raw["mean"], "chain_var": raw["var"], "acov": raw["acov"],
+           "hmean": raw["hmean"], "hvar": raw["hvar"], "flags": raw["flags"].astype(np.uint32),
+           "names": [f"beta{j + 1}" for j in range(P)] + ["sig2", "tau", "alpha"],
+           "nsamp": int(nsamp), "maxlag": int(maxlag), "p": int(P)}
+    out.update(sum_stat_from_summary(dict(raw, nsamp=nsamp, p=P), runtime))
+    return out
+
+
+def _chains_summary(entry: str, tri: bool, y, X, nsamp, nchains, alpha, sig2_shape, sig2_scale,
+                    nu_shape, nu_rate, alpha_a, alpha_b, sig2_true, tau_true, burn, ortho,
+                    betaburn, maxlag):
+    L = library()
+    _require_gpu()
+    y = np.asarray(y, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    R, P = X.shape
+    N = y.shape[0]
+    M, K = int(nsamp), int(nchains)
+    if not check_parameters(N, R, M, sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                            alpha_b) or not _is_above(K, 1, "nchains"):
+        raise ValueError(f"{entry}: invalid parameters")
+    lag = _summary_maxlag(M, maxlag)
+    if not 0 <= lag <= SUMMARY_MAX_LAG:
+        raise ValueError(f"{entry}: maxlag must be in [0, {SUMMARY_MAX_LAG}] (got {lag})")
+    raw = _summary_buffers(K, P + 3, lag)
+    d = lambda v: ctypes.byref(ctypes.c_double(float(v)))  # noqa: E731
+    i = lambda v: ctypes.byref(ctypes.c_int(int(v)))  # noqa: E731
+    rt = ctypes.c_double(0.0)
+    Xf = np.asfortranarray(X)
+    args = [_p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]), _p(raw["hmean"]), _p(raw["hvar"]),
+            raw["flags"].ctypes.data_as(_ip), i(lag), _p(y), _p(Xf), d(sig2_shape),
+            d(sig2_scale), d(nu_shape), d(nu_rate), d(alpha_a), d(alpha_b), d(sig2_true),
+            d(tau_true), d(alpha), i(P), i(N), i(M), i(burn), ctypes.byref(rt),
+            i(1 if ortho else 0)]
+    if tri:
+        L.bridge_regression_chains_summary(*args, i(betaburn), i(0), i(K))
+    else:
+        L.bridge_reg_stable_chains_summary(*args, i(K))
+    if np.isnan(raw["mean"]).all() and rt.value == 0.0:
+        raise RuntimeError(f"{entry}: the call returned no summaries: {_err()}")
+    return _summary_result(raw, P, M, lag, rt.value)
+
+
+def bridge_reg_stb_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0,
+                                  sig2_scale=0.0, nu_shape=2.0, nu_rate=2.0, alpha_a=1.0,
+                                  alpha_b=1.0, sig2_true=0.0, tau_true=0.0, burn=500,
+                                  ortho=False, maxlag=None):
+    """``bridge_reg_stb_chains`` returning posterior summaries instead of traces, through
+    ``.C("bridge_reg_stable_chains_summary", ...)``: the chains are bit for bit those of the
+    trace call under the same key, each ring fill is reduced on the device and nothing but the
+    summaries is copied, so ``nsamp`` and ``nchains`` are not bounded by host memory.
+
+    Parameters are beta_1..beta_P, sig2, tau, alpha (Q = P + 3, ``names``).  Returns a dict:
+    chain_mean, chain_var (K x Q), acov (K x Q x maxlag + 1, biased autocovariances), hmean,
+    hvar (K x Q x 2, the halves of split R-hat), flags (K), names, nsamp, maxlag, p, and the keys
+    of ``diagnostics.sum_stat_chains`` for the coefficients (mean, sd, ess, esr, rhat,
+    ess_summary, esr_summary, runtime, chains), so a script can switch between the two calls.
+    ``maxlag=None`` is min(63, coda's default order)."""
+    return _chains_summary("bridge_reg_stb_chains_summary", False, y, X, nsamp, nchains, alpha,
+                           sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
+                           sig2_true, tau_true, burn, ortho, 0, maxlag)
+
+
+def bridge_reg_tri_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0,
+                                  sig2_scale=0.0, nu_shape=2.0, nu_rate=2.0, alpha_a=1.0,
+                                  alpha_b=1.0, sig2_true=0.0, tau_true=0.0, burn=500,
+                                  ortho=False, betaburn=0, maxlag=None):
+    """``bridge_reg_tri_chains`` returning posterior summaries instead of traces, through
+    ``.C("bridge_regression_chains_summary", ...)``; see ``bridge_reg_stb_chains_summary``."""
+    return _chains_summary("bridge_reg_tri_chains_summary", True, y, X, nsamp, nchains, alpha,
+                           sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
+                           sig2_true, tau_true, burn, ortho, betaburn, maxlag)
+
+
+def trace_summary(x, maxlag, chunk=None):
+    """The trace-summary kernel on host data (bb_trace_summary): x is (K, M, Q) (a (M, Q) array
+    is one chain), accumulated ``chunk`` samples at a time (None: all at once).  Returns a dict:
+    mean, var (K, Q), acov (K, Q, maxlag + 1), hmean, hvar (K, Q, 2)."""
+    L = library()
+    _require_gpu()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    K, M, Q = x.shape
+    lag = int(maxlag)
+    raw = _summary_buffers(K, Q, lag)
+    del raw["flags"]
+    _check(L.bb_trace_summary(_p(x), K, M, Q, lag, int(M if chunk is None else chunk),
+                              _p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]),
+                              _p(raw["hmean"]), _p(raw["hvar"])), "bb_trace_summary")
+    return raw
 
 
 def bridge_reg_logit(y, X, nsamp, alpha=0.5, nu_shape=2.0, nu_rate=2.0, alpha_a=1.0,
@@ -1350,6 +1481,29 @@ class ChainBatch:
         _check(library().bb_chains_get_tri_basis(self._h, _p(tV), _p(a), _p(d)),
                "bb_chains_get_tri_basis")
         return tV, a, d
+
+    def summary_reset(self, nsamp: int, maxlag=None):
+        """Create and zero the device-side summary of every chain for ``nsamp`` samples."""
+        self._sum = (int(nsamp), _summary_maxlag(nsamp, maxlag))
+        _check(library().bb_chains_summary_reset(self._h, *self._sum), "bb_chains_summary_reset")
+
+    def summary_add(self, slot0: int, count: int, s0: int):
+        """Add ring slots [slot0, slot0 + count) of every chain as the samples s0 .. (in order,
+        behind the runs that wrote them; does not wait)."""
+        _check(library().bb_chains_summary_add(self._h, int(slot0), int(count), int(s0)),
+               "bb_chains_summary_add")
+
+    def summary(self):
+        """The summaries once all samples are in: mean, var (K, Q), acov (K, Q, maxlag + 1),
+        hmean, hvar (K, Q, 2), flags (K); Q = p + 3 (beta, sig2, tau, alpha)."""
+        nsamp, lag = getattr(self, "_sum", (0, 0))
+        raw = _summary_buffers(self.nchains, self.p + 3, lag)
+        _check(library().bb_chains_summary_get(
+            self._h, _p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]), _p(raw["hmean"]),
+            _p(raw["hvar"]), raw["flags"].ctypes.data_as(_ip)), "bb_chains_summary_get")
+        raw["flags"] = raw["flags"].astype(np.uint32)
+        raw.update(nsamp=nsamp, maxlag=lag, p=self.p)
+        return raw
 
     def threads(self) -> int:
         """Threads per workgroup of the kernel instance this batch runs."""

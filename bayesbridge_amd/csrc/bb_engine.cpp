@@ -1509,18 +1509,6 @@ void ring_copy(double *dst, const double *src, size_t count) {
     HIPCHECK(hipMemcpy(dst, src, count * sizeof(double), hipMemcpyDeviceToHost));
 }
 
-// f(k, slot, run) for each contiguous run of the slots [slot0, slot0 + count) in a ring of
-// `cap`: slots slot .. slot + run - 1 hold the samples k .. k + run - 1 of the request
-template <class F>
-void ring_runs(int slot0, int count, int cap, F f) {
-    for (int k = 0; k < count;) {
-        const int slot = (slot0 + k) % cap;
-        const int run = std::min(count - k, cap - slot);
-        f(k, slot, run);
-        k += run;
-    }
-}
-
 // Ring slots [slot0, slot0 + count) of some traces to the host: each is `w` doubles per slot
 // from `ring` (slot 0 of the ring) to `dst`, skipped when dst is null.
 struct RingTrace {
@@ -1561,6 +1549,19 @@ struct Traces {
         auto at = [&](double *q, size_t w) { return q ? q + k * w * m : nullptr; };
         return {at(beta, p), at(lam, p), at(sig2, 1), at(tau, 1), at(alpha, 1), at(u, p),
                 at(shape, p)};
+    }
+};
+
+// The outputs of a .C summary call, K chains of Q = P + 3 parameters (beta, sig2, tau, alpha):
+// mean, var Q x K, acov (L + 1) x Q x K, hmean, hvar 2 x Q x K column-major, flags K.
+struct SummaryOut {
+    double *mean, *var, *acov, *hmean, *hvar;
+    int *flags;
+    int maxlag;
+    // chain k's slice
+    SummaryOut chain(size_t k, size_t q) const {
+        return {mean + k * q, var + k * q, acov + k * q * (maxlag + 1), hmean + 2 * k * q,
+                hvar + 2 * k * q, flags + k, maxlag};
     }
 };
 
@@ -1714,6 +1715,32 @@ struct bb_chains {
             strided(o.u, tr_u, (size_t)p, k, sl, run);
             strided(o.shape, tr_shape, (size_t)p, k, sl, run);
         });
+    }
+
+    // The optional device-side summary of all K chains (bb_summary.hip): created by
+    // summary_reset, fed ring slots on the batch's stream behind the sweeps that wrote them.
+    std::unique_ptr<TraceSummary> summary;
+    SummaryRing summary_ring() const {
+        return {.beta = tr_beta, .sig2 = tr_sig2, .tau = tr_tau, .alpha = tr_alpha, .p = p,
+                .cap = cap};
+    }
+    void summary_reset(int nsamp, int maxlag) {
+        if (!summary) summary.reset(new TraceSummary());
+        summary->reset(stream(), K, p + 3, nsamp, maxlag);
+    }
+    void summary_add(int slot0, int count, int s0) {
+        if (!summary) throw HipError("summary: add before reset");
+        summary->add(stream(), summary_ring(), slot0, count, s0);
+    }
+    // the summaries and every chain's error word (any output may be null)
+    void summary_get(double *mean, double *var, double *acov, double *hmean, double *hvar,
+                     int *flags) {
+        if (!summary) throw HipError("summary: get before reset");
+        summary->get(stream(), mean, var, acov, hmean, hvar);
+        if (flags) {
+            static_assert(sizeof(int) == sizeof(uint32_t), "flags are 32-bit words");
+            HIPCHECK(hipMemcpy(flags, err, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
     }
 
     uint64_t base_stream = 0;
@@ -2313,6 +2340,20 @@ int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d) {
         return -1;
     }
     return bb_engine_get_tri_basis(b->proto, tV, a, d);
+}
+
+int bb_chains_summary_reset(bb_chains *b, int nsamp, int maxlag) {
+    return guarded(b->proto->cfg.device, [&] { b->summary_reset(nsamp, maxlag); });
+}
+
+int bb_chains_summary_add(bb_chains *b, int slot0, int count, int s0) {
+    return guarded(b->proto->cfg.device, [&] { b->summary_add(slot0, count, s0); });
+}
+
+int bb_chains_summary_get(bb_chains *b, double *mean, double *var, double *acov, double *hmean,
+                          double *hvar, int *flags) {
+    return guarded(b->proto->cfg.device,
+                   [&] { b->summary_get(mean, var, acov, hmean, hvar, flags); });
 }
 
 // ~0u when the flags cannot be read; bb_last_error then says why and is empty otherwise, which
@@ -2980,8 +3021,11 @@ struct ChainsRun {
 
 // K chains of a small design as one batch on drive_chain's schedule (50-sweep blocks, as a
 // fused single chain).  The trace budget bounds the batch: each chain's ring gets a K-th.
+// With `sum` the ring fills are not copied out but reduced on the device behind the sweeps
+// (bb_chains::summary_add), and the summaries come back after a complete run.
 Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const double *yp,
-                     const double *Xp, int b, const Traces &out, double *runtime) {
+                     const double *Xp, int b, const Traces &out, double *runtime,
+                     const SummaryOut *sum = nullptr) {
     const int m = c0.trace_capacity;
     *runtime = 0.0;
     bb_config c = c0;
@@ -2992,10 +3036,14 @@ Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const doubl
     g_last_devices = 1;
     g_last_capacity = ch->cap;
     ChainsRun run{raw, ch->cap};
-    return drive_schedule(
+    if (sum && bb_chains_summary_reset(raw, m, sum->maxlag) != 0) return OUT_ERROR;
+    const Outcome o = drive_schedule(
         run, 50, kd.nburn, kd.t_base, m, b, runtime,
         [&](int slot0, int count, int s0) {
-            ch->copy_out(slot0, count, s0, m, out);
+            if (sum)
+                ch->summary_add(slot0, count, s0);
+            else
+                ch->copy_out(slot0, count, s0, m, out);
             return 0;
         },
         [&] {
@@ -3007,6 +3055,11 @@ Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const doubl
                     print_abort("numerical failure in the device sampler (flags %u) in chain %i",
                                 f[k], k);
         });
+    if (sum && o == OUT_OK &&
+        bb_chains_summary_get(raw, sum->mean, sum->var, sum->acov, sum->hmean, sum->hvar,
+                              sum->flags) != 0)
+        return OUT_ERROR;
+    return o;
 }
 
 // bridge_reg_stable_chains / bridge_regression_chains: the batch where the fused small chain
@@ -3033,6 +3086,100 @@ Outcome chains_call(const CallKind &kd, const bb_config &c, int K, const double 
         const Outcome o = dense_call(kd, ck, yp, Xp, b, out.chain(k, c.p, m), &rt);
         *runtime += rt;
         if (o == OUT_INTERRUPTED) return o;
+    }
+    return OUT_OK;
+}
+
+// One chain of a summary call on a single engine: its ring ([slot][p], tr_sig2 / tr_tau /
+// tr_alpha) is reduced by the chain batch's kernel with one chain.  An interrupted or failed
+// run leaves the outputs as they were.
+Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const double *yp,
+                           const double *Xp, const SummaryOut &out, double *runtime) {
+    const int m = c.trace_capacity, n = c.n;
+    print_banner(kd.title, c, b, m);
+    g_last_interrupted = 0;
+    *runtime = 0.0;
+    Outcome o;
+    {
+        Chain ch;
+        if (chain_build(ch, c, kd.ntr,
+                        [&](const bb_config *cc, int j0, int, bb_engine **e) {
+                            return bb_engine_create(cc, Xp + (size_t)j0 * n, yp, e);
+                        }) != 0 ||
+            ch.eng.size() != 1) {
+            if (ch.eng.size() > 1) set_error("summaries need every column on one device");
+            print_abort("%s", g_last_error.c_str());
+            return OUT_ERROR;
+        }
+        g_last_devices = 1;
+        g_last_capacity = ch.cap;
+        bb_engine *e = ch.eng[0];
+        TraceSummary ts;
+        const SummaryRing ring{.beta = e->tr_beta, .sig2 = e->tr_sig2, .tau = e->tr_tau,
+                               .alpha = e->tr_alpha, .p = e->p_loc, .cap = ch.cap};
+        o = (Outcome)guarded(e->cfg.device, [&] {
+            ts.reset(e->stream, 1, c.p + 3, m, out.maxlag);
+            return (int)OUT_OK;
+        });
+        if (o != OUT_OK) o = OUT_ERROR;
+        if (o == OUT_OK)
+            o = drive_schedule(
+                ch, ch.fused() ? 50 : 10, kd.nburn, kd.t_base, m, b, runtime,
+                [&](int slot0, int count, int s0) {
+                    HIPCHECK(hipSetDevice(e->cfg.device));
+                    ts.add(e->stream, ring, slot0, count, s0);
+                    return 0;
+                },
+                [&] {
+                    const uint32_t f = ch.flags();
+                    if (f & ~4u)
+                        print_abort("numerical failure in the device sampler (flags %u)", f);
+                });
+        if (o == OUT_OK &&
+            guarded(e->cfg.device, [&] {
+                ts.get(e->stream, out.mean, out.var, out.acov, out.hmean, out.hvar);
+                *out.flags = (int)ch.flags();
+            }) != 0)
+            o = OUT_ERROR;
+        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
+    }
+    if (g_verbose && o == OUT_OK)
+        printf("Sampling complete: %g sec. for %i iterations.\n", *runtime, m);
+    g_last_interrupted = o == OUT_INTERRUPTED;
+    return o;
+}
+
+// bridge_reg_stable_chains_summary / bridge_regression_chains_summary: chains_call with the
+// ring fills reduced on the device and only the summaries returned.  A chain that would be
+// sharded by columns over several devices is refused: every column has to be on one device.
+Outcome chains_summary_call(const char *entry, const CallKind &kd, const bb_config &c, int K,
+                            const double *yp, const double *Xp, int b, const SummaryOut &out,
+                            double *runtime) {
+    const int m = c.trace_capacity;
+    *runtime = 0.0;
+    if (chains_refusal(c) == nullptr) {
+        print_banner(kd.title, c, b, m);
+        g_last_interrupted = 0;
+        const Outcome o = chains_batch(kd, c, K, yp, Xp, b, Traces{}, runtime, &out);
+        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
+        if (g_verbose && o == OUT_OK)
+            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime, m, K);
+        g_last_interrupted = o == OUT_INTERRUPTED;
+        return o;
+    }
+    if (const int ndev = chain_devices(c); ndev > 1) {
+        set_error("%s: this design would be sharded by columns over %d devices; summaries need "
+                  "every column on one device (bb_set_device_count(1))", entry, ndev);
+        print_abort("%s", g_last_error.c_str());
+        return OUT_ERROR;
+    }
+    for (int k = 0; k < K; ++k) {
+        bb_config ck = c;
+        ck.stream = c.stream + (uint64_t)k;
+        double rt = 0.0;
+        const Outcome o = summary_chain_call(kd, ck, b, yp, Xp, out.chain(k, c.p + 3), &rt);
+        *runtime += rt;
+        if (o != OUT_OK) return o;
     }
     return OUT_OK;
 }
@@ -3088,6 +3235,16 @@ Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, Trace
 bool nchains_ok(const char *entry, int nchains) {
     if (nchains >= 1) return true;
     set_error("%s: nchains must be at least 1 (got %d)", entry, nchains);
+    printf("Error: %s\n", g_last_error.c_str());
+    fflush(stdout);
+    return false;
+}
+
+// a summary entry's (nsamp, maxlag), checked like nchains
+bool summary_args_ok(const char *entry, int nsamp, int maxlag) {
+    const char *why = TraceSummary::refusal(nsamp, maxlag);
+    if (!why) return true;
+    set_error("%s: %s (got maxlag %d, %d samples)", entry, why, maxlag, nsamp);
     printf("Error: %s\n", g_last_error.c_str());
     fflush(stdout);
     return false;
@@ -3251,6 +3408,27 @@ void bridge_reg_stable_chains(double *betap, double *lambdap, double *sig2p, dou
         reraise_interrupt();
 }
 
+void bridge_reg_stable_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
+                                      double *hvarp, int *flagsp, const int *maxlag,
+                                      const double *yp, const double *Xp,
+                                      const double *sig2_shape, const double *sig2_scale,
+                                      const double *nu_shape, const double *nu_rate,
+                                      const double *alpha_a, const double *alpha_b,
+                                      const double *true_sig2, const double *true_tau,
+                                      const double *true_alpha, const int *P, const int *N,
+                                      const int *M, const int *burn, double *runtime,
+                                      const int *ortho, const int *nchains) {
+    const char *entry = "bridge_reg_stable_chains_summary";
+    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag)) return;
+    const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                           alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                           ortho, *nchains);
+    if (chains_summary_call(entry, stable_kind(*burn), c, *nchains, yp, Xp, *burn,
+                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag},
+                            runtime) == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
 void bridge_reg_stable_csc(double *betap, double *lambdap, double *sig2p, double *taup,
                            double *alphap, const double *yp, const int *Xcolptr,
                            const int *Xrowidx, const double *Xval, const double *sig2_shape,
@@ -3315,6 +3493,29 @@ void bridge_regression_chains(double *betap, double *up, double *omegap, double 
                                         ortho, betaburn, *nchains);
     if (chains_call(tri_kind(*burn), c, *nchains, yp, Xp, *burn,
                     {betap, omegap, sig2p, taup, alphap, up, shapep}, runtime) == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
+void bridge_regression_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
+                                      double *hvarp, int *flagsp, const int *maxlag,
+                                      const double *yp, const double *Xp,
+                                      const double *sig2_shape, const double *sig2_scale,
+                                      const double *nu_shape, const double *nu_rate,
+                                      const double *alpha_a, const double *alpha_b,
+                                      const double *true_sig2, const double *true_tau,
+                                      const double *true_alpha, const int *P, const int *N,
+                                      const int *M, const int *burn, double *runtime,
+                                      const int *ortho, const int *betaburn, const int *use_hmc,
+                                      const int *nchains) {
+    (void)use_hmc;
+    const char *entry = "bridge_regression_chains_summary";
+    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag)) return;
+    const bb_config c = tri_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                        alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                        ortho, betaburn, *nchains);
+    if (chains_summary_call(entry, tri_kind(*burn), c, *nchains, yp, Xp, *burn,
+                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag},
+                            runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 

@@ -127,6 +127,106 @@ struct Scratch {
     }
 };
 
+// f(k, slot, run) for each contiguous run of the slots [slot0, slot0 + count) in a ring of
+// `cap`: slots slot .. slot + run - 1 hold the samples k .. k + run - 1 of the request
+template <class F>
+void ring_runs(int slot0, int count, int cap, F f) {
+    for (int k = 0; k < count;) {
+        const int slot = (slot0 + k) % cap;
+        const int run = std::min(count - k, cap - slot);
+        f(k, slot, run);
+        k += run;
+    }
+}
+
+// Posterior summaries of K chains' trace rings, accumulated on the device (bb_summary.hip;
+// the records and their layout: bb_kernels.h): reset(), then the M samples in order through
+// add() as the rings fill, then get().  Everything is enqueued on the caller's stream, behind
+// the sweeps that wrote the slots; the current device is the caller's.
+struct TraceSummary {
+    int K = 0, Q = 0, M = 0, L = 0;
+    int next = 0;  // samples added so far
+    double *acc = nullptr, *out = nullptr;
+    size_t acc_count = 0, out_count = 0;
+    TraceSummary() = default;
+    TraceSummary(const TraceSummary &) = delete;
+    TraceSummary &operator=(const TraceSummary &) = delete;
+    ~TraceSummary() {
+        (void)hipFree(acc);
+        (void)hipFree(out);
+    }
+    // doubles of the outputs per (chain, parameter): mean, var, acov[0..L], hmean[2], hvar[2]
+    static size_t out_per_record(int L) { return (size_t)(L + 1) + 6; }
+    // why (nsamp, maxlag) cannot be summarised, or nullptr
+    static const char *refusal(int nsamp, int maxlag) {
+        if (maxlag < 0) return "maxlag must be at least 0";
+        if (maxlag > kSummaryMaxLag) return "maxlag must be at most 63 (a lag per lane of a wave)";
+        if (nsamp < 1) return "the number of samples must be at least 1";
+        return nullptr;
+    }
+    // sized for K chains of Q parameters, M samples and lags 0..L, and zeroed
+    void reset(hipStream_t s, int K_, int Q_, int M_, int L_) {
+        if (const char *why = refusal(M_, L_)) throw HipError(std::string("summary: ") + why);
+        if (K_ < 1 || Q_ < 1) throw HipError("summary: no chains or no parameters");
+        const size_t na = (size_t)K_ * Q_ * kSummaryStride;
+        const size_t no = (size_t)K_ * Q_ * out_per_record(L_);
+        auto fit = [&](double *&q, size_t &have, size_t need) {
+            if (have == need) return;
+            HIPCHECK(hipStreamSynchronize(s));
+            (void)hipFree(q);
+            q = nullptr;
+            have = 0;
+            HIPCHECK(hipMalloc((void **)&q, need * sizeof(double)));
+            have = need;
+        };
+        fit(acc, acc_count, na);
+        fit(out, out_count, no);
+        K = K_, Q = Q_, M = M_, L = L_, next = 0;
+        HIPCHECK(hipMemsetAsync(acc, 0, na * sizeof(double), s));
+    }
+    // ring slots [slot0, slot0 + count) (wrapping at ring.cap) are the samples [s0, s0 + count)
+    void add(hipStream_t s, const SummaryRing &ring, int slot0, int count, int s0) {
+        if (!acc) throw HipError("summary: add before reset");
+        if (ring.params() != Q) throw HipError("summary: the rings hold another parameter count");
+        if (slot0 < 0 || count < 0) throw HipError("summary: slot0 and count must be >= 0");
+        if (s0 != next || count > M - next) {
+            char b[160];
+            snprintf(b, sizeof(b), "summary: samples are added in order (next %d of %d; got %d "
+                     "from %d)", next, M, count, s0);
+            throw HipError(b);
+        }
+        ring_runs(slot0, count, ring.cap, [&](int k, int slot, int run) {
+            launch_trace_summary(s, ring, K, slot, run, s0 + k, M, L, acc);
+        });
+        HIPCHECK(hipGetLastError());
+        next += count;
+    }
+    // The outputs to the host once all M samples are in, chain-major: mean, var [K][Q], acov
+    // [K][Q][L + 1], hmean, hvar [K][Q][2].  Waits for the stream.
+    void get(hipStream_t s, double *mean, double *var, double *acov, double *hmean,
+             double *hvar) {
+        if (!acc || next != M) {
+            char b[128];
+            snprintf(b, sizeof(b), "summary: %d of %d samples added", acc ? next : 0, M);
+            throw HipError(b);
+        }
+        const size_t kq = (size_t)K * Q;
+        double *dm = out, *dv = dm + kq, *da = dv + kq, *dhm = da + kq * (L + 1),
+               *dhv = dhm + 2 * kq;
+        launch_summary_finalise(s, acc, K, Q, M, L, dm, dv, da, dhm, dhv);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(s));
+        auto fetch = [&](double *dst, const double *src, size_t n) {
+            if (dst) HIPCHECK(hipMemcpy(dst, src, n * sizeof(double), hipMemcpyDeviceToHost));
+        };
+        fetch(mean, dm, kq);
+        fetch(var, dv, kq);
+        fetch(acov, da, kq * (L + 1));
+        fetch(hmean, dhm, 2 * kq);
+        fetch(hvar, dhv, 2 * kq);
+    }
+};
+
 // ---------------------------------------------------------------------------
 // Sparse design (CSC input): CSC + CSR copies on the device and the Gram pair list
 // (bb_sparse.h).  Built once at setup; X is constant over a chain.

@@ -445,6 +445,33 @@ int launch_tri_chains(hipStream_t s, int nchains, int threads, const ChainDesign
 int tri_chains_resident_per_cu(int n, int p, int threads);
 int tri_chains_threads(int n, int p, int nchains, int cus);  // the instance a batch runs
 
+// Posterior summaries of trace rings on the device (bb_summary.hip): per chain c
+// and parameter q (beta_1..beta_p, then sig2, tau, alpha) the running sums from which the mean,
+// the variance, the autocovariances at lags 0..L (L <= kSummaryMaxLag) and the moments of the
+// two halves follow.  With z_t = x_t - x_0, lane k of the (c, q) record carries
+//   S_k = sum_{t >= k} z_t z_{t-k},  H_k = sum_{t < k} z_t,  W_k = z_{last-k} (the window),
+// and its tail T = sum z_t, x_0, and sum z, sum z^2 of each half.  Each is one running sum in
+// sample order, so the result does not depend on how the samples were split over launches.
+constexpr int kSummaryMaxLag = 63;
+constexpr int kSummaryLanes = kSummaryMaxLag + 1;
+enum { SUM_T = 3 * kSummaryLanes, SUM_X0, SUM_HS0, SUM_HS1, SUM_HQ0, SUM_HQ1, SUM_PAD0, SUM_PAD1,
+       kSummaryStride };  // doubles per (chain, parameter) record: S, H, W, then the tail
+// The rings a summary reads: chain c's slot s is beta[(c cap + s) p + j] and sig2[c cap + s],
+// ... (a single engine: one chain).  sig2 == nullptr: beta alone (Q = p), else Q = p + 3.
+struct SummaryRing {
+    const double *beta, *sig2 = nullptr, *tau = nullptr, *alpha = nullptr;
+    int p, cap;
+    int params() const { return p + (sig2 ? 3 : 0); }
+};
+// Adds ring slots [slot, slot + count) (no wrap: slot + count <= cap) of each of K chains as
+// the samples s0 .. s0 + count - 1 of M to acc ([K][Q][kSummaryStride], zeroed before sample 0).
+void launch_trace_summary(hipStream_t s, const SummaryRing &r, int K, int slot, int count, int s0,
+                          int M, int L, double *acc);
+// acc after all M samples -> mean, var [K][Q], acov [K][Q][L + 1], hmean, hvar [K][Q][2]
+void launch_summary_finalise(hipStream_t s, const double *acc, int K, int Q, int M, int L,
+                             double *mean, double *var, double *acov, double *hmean,
+                             double *hvar);
+
 // Copy the scalars into trace slots (known parameters / alpha when known).
 void launch_record_scalars(hipStream_t s, const DevScalars *sc, double *tau_tr,
                            double *sig2_tr, double *alpha_tr);

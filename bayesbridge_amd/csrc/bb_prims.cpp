@@ -246,6 +246,41 @@ int bb_gram(double *C, const double *Yh, const double *wh, int n, int k) {
     });
 }
 
+int bb_trace_summary(const double *x, int K, int M, int Q, int maxlag, int chunk, double *mean,
+                     double *var, double *acov, double *hmean, double *hvar) {
+    if (const char *why = TraceSummary::refusal(M, maxlag)) {
+        set_error("bb_trace_summary: %s (got maxlag %d, %d samples)", why, maxlag, M);
+        return -1;
+    }
+    if (K < 1 || Q < 1 || chunk < 1) {
+        set_error("bb_trace_summary: K, Q and chunk must be at least 1");
+        return -1;
+    }
+    return guarded(g_device, [&] {
+        Scratch dev;
+        // the rings as a chain batch lays them out: [chain][slot][P] and, for Q > 3, the last
+        // three columns as the scalar rings [chain][slot]
+        const int P = Q > 3 ? Q - 3 : Q;
+        const size_t slots = (size_t)K * M;
+        double *db = dev.alloc<double>(slots * P), *ds = nullptr;
+        HIPCHECK(hipMemcpy2D(db, (size_t)P * sizeof(double), x, (size_t)Q * sizeof(double),
+                             (size_t)P * sizeof(double), slots, hipMemcpyHostToDevice));
+        if (P < Q) {
+            ds = dev.alloc<double>(3 * slots);
+            for (int j = 0; j < 3; ++j)
+                HIPCHECK(hipMemcpy2D(ds + j * slots, sizeof(double), x + P + j,
+                                     (size_t)Q * sizeof(double), sizeof(double), slots,
+                                     hipMemcpyHostToDevice));
+        }
+        SummaryRing ring{.beta = db, .p = P, .cap = M};
+        if (ds) ring.sig2 = ds, ring.tau = ds + slots, ring.alpha = ds + 2 * slots;
+        TraceSummary ts;
+        ts.reset(0, K, Q, M, maxlag);
+        for (int s = 0; s < M; s += chunk) ts.add(0, ring, s, std::min(chunk, M - s), s);
+        ts.get(0, mean, var, acov, hmean, hvar);
+    });
+}
+
 int bb_gram_ozaki(double *C, const double *Yh, const double *wh, int n, int k) {
     return guarded(g_device, [&] {
         Scratch dev;

@@ -11,7 +11,13 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["effective_size", "sum_stat", "rhat", "sum_stat_chains"]
+__all__ = ["effective_size", "sum_stat", "rhat", "sum_stat_chains", "effective_size_from_acov",
+           "rhat_from_moments", "sum_stat_from_summary", "default_maxlag"]
+
+
+def default_maxlag(n: int) -> int:
+    """coda's largest autoregressive order for n samples: floor(min(n - 1, 10 log10 n))."""
+    return max(0, int(np.floor(min(n - 1, 10 * np.log10(n)))))
 
 
 def _acov(x: np.ndarray, maxlag: int) -> np.ndarray:
@@ -30,9 +36,14 @@ def _ar_yw_aic(x: np.ndarray, order_max: int | None = None):
     Returns (coefficients, var.pred)."""
     n = x.shape[0]
     if order_max is None:
-        order_max = int(np.floor(min(n - 1, 10 * np.log10(n))))
+        order_max = default_maxlag(n)
     order_max = max(0, min(order_max, n - 1))
-    r = _acov(x, order_max)
+    return _ar_from_acov(n, _acov(x, order_max))
+
+
+def _ar_from_acov(n: int, r: np.ndarray):
+    """_ar_yw_aic from the biased autocovariances r[0..order_max] of n samples."""
+    order_max = max(0, min(len(r) - 1, n - 1))
     if r[0] <= 0:
         return np.zeros(0), 0.0
     # Levinson-Durbin recursion
@@ -56,6 +67,12 @@ def _ar_yw_aic(x: np.ndarray, order_max: int | None = None):
     return ar, var_pred
 
 
+def _ess(n: int, var: float, ar: np.ndarray, var_pred: float) -> float:
+    """n var / spectrum0 of the fitted autoregression, 0 where the spectral estimate is 0."""
+    spec = var_pred / (1.0 - ar.sum()) ** 2
+    return 0.0 if spec == 0 else n * var / spec
+
+
 def effective_size(x) -> np.ndarray:
     """coda::effectiveSize of each column of x (samples x parameters; a 1-D trace is one
     parameter): n var(x) / spectrum0.ar(x), 0 where the spectral estimate is 0."""
@@ -69,10 +86,26 @@ def effective_size(x) -> np.ndarray:
         if np.all(col == col[0]):
             out[j] = 0.0
             continue
-        ar, vp = _ar_yw_aic(col)
-        spec = vp / (1.0 - ar.sum()) ** 2
-        out[j] = 0.0 if spec == 0 else n * col.var(ddof=1) / spec
+        out[j] = _ess(n, col.var(ddof=1), *_ar_yw_aic(col))
     return out
+
+
+def effective_size_from_acov(n: int, acov) -> np.ndarray:
+    """effective_size with the autocovariances given: acov[..., k] is the biased
+    autocovariance (divisor n, centred at the trace's mean) at lag k = 0..L of a trace of n
+    samples, L the largest autoregressive order tried (coda tries default_maxlag(n)).  The
+    unbiased variance is acov[..., 0] n / (n - 1); a zero-variance trace returns 0."""
+    acov = np.asarray(acov, dtype=np.float64)
+    flat = acov.reshape(-1, acov.shape[-1])
+    out = np.zeros(flat.shape[0])
+    for j, r in enumerate(flat):
+        if r[0] == 0:
+            continue
+        if not np.isfinite(r[0]):
+            out[j] = np.nan
+            continue
+        out[j] = _ess(n, r[0] * n / (n - 1), *_ar_from_acov(n, r))
+    return out.reshape(acov.shape[:-1])
 
 
 def sum_stat(beta, runtime: float):
@@ -99,10 +132,30 @@ def rhat(x) -> np.ndarray:
     if n < 2:
         raise ValueError("rhat: at least four draws per chain are needed")
     seq = np.concatenate([x[:, :n], x[:, x.shape[1] - n:]], axis=0)  # (2K, n[, P])
-    W = seq.var(axis=1, ddof=1).mean(axis=0)
-    B_over_n = seq.mean(axis=1).var(axis=0, ddof=1)
+    return _rhat_of_sequences(n, seq.mean(axis=1), seq.var(axis=1, ddof=1))
+
+
+def _rhat_of_sequences(n: int, means, variances) -> np.ndarray:
+    """R-hat from the means and unbiased variances (sequences first) of sequences of length n."""
+    W = variances.mean(axis=0)
+    B_over_n = means.var(axis=0, ddof=1)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.sqrt((n - 1) / n + B_over_n / W)
+
+
+def rhat_from_moments(n: int, hmean, hvar) -> np.ndarray:
+    """rhat from the moments of the halves: n is the number of draws per chain, hmean and hvar
+    are (K, 2) or (K, P, 2), the mean and unbiased variance of the first and of the last
+    n // 2 draws of each chain."""
+    hmean = np.asarray(hmean, dtype=np.float64)
+    hvar = np.asarray(hvar, dtype=np.float64)
+    if hmean.ndim not in (2, 3) or hmean.shape[-1] != 2 or hvar.shape != hmean.shape:
+        raise ValueError("rhat_from_moments: hmean and hvar must be (chains[, parameters], 2)")
+    if n // 2 < 2:
+        raise ValueError("rhat: at least four draws per chain are needed")
+    # the 2K sequences in rhat's order: every chain's first half, then every chain's second
+    seq = lambda a: np.concatenate([a[..., 0], a[..., 1]], axis=0)  # noqa: E731
+    return _rhat_of_sequences(n // 2, seq(hmean), seq(hvar))
 
 
 def sum_stat_chains(beta, runtime: float):
@@ -120,6 +173,35 @@ def sum_stat_chains(beta, runtime: float):
     pooled = beta.reshape(K * M, P)
     return {"mean": pooled.mean(axis=0), "sd": pooled.std(axis=0, ddof=1), "ess": ess,
             "esr": esr, "rhat": rhat(beta),
+            "ess_summary": (float(ess.min()), float(np.median(ess)), float(ess.max())),
+            "esr_summary": (float(esr.min()), float(np.median(esr)), float(esr.max())),
+            "runtime": runtime, "chains": K}
+
+
+def sum_stat_from_summary(summary, runtime: float):
+    """sum_stat_chains from the per-chain moments a summary call returns, without the traces:
+    summary has nsamp, mean and var (K, Q), acov (K, Q, L + 1), hmean and hvar (K, Q, 2)
+    (optionally p: only the first p parameters, the coefficients, are summarised).  The pooled
+    mean and sd merge the chains' moments (Chan et al.), the ESS is each chain's
+    effective_size_from_acov summed, R-hat is rhat_from_moments."""
+    M = int(summary["nsamp"])
+    P = int(summary.get("p", np.asarray(summary["mean"]).shape[1]))
+    mean = np.asarray(summary["mean"], dtype=np.float64)[:, :P]
+    var = np.asarray(summary["var"], dtype=np.float64)[:, :P]
+    acov = np.asarray(summary["acov"], dtype=np.float64)[:, :P]
+    K = mean.shape[0]
+    ess = effective_size_from_acov(M, acov).sum(axis=0)
+    esr = ess / runtime if runtime > 0 else np.full_like(ess, np.inf)
+    pooled = mean.mean(axis=0)  # equal chain lengths
+    m2 = ((M - 1) * var).sum(axis=0) + M * ((mean - pooled) ** 2).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sd = np.sqrt(m2 / (K * M - 1))
+    if M // 2 >= 2:
+        r = rhat_from_moments(M, np.asarray(summary["hmean"])[:, :P],
+                              np.asarray(summary["hvar"])[:, :P])
+    else:
+        r = np.full(P, np.nan)
+    return {"mean": pooled, "sd": sd, "ess": ess, "esr": esr, "rhat": r,
             "ess_summary": (float(ess.min()), float(np.median(ess)), float(ess.max())),
             "esr_summary": (float(esr.min()), float(np.median(esr)), float(esr.max())),
             "runtime": runtime, "chains": K}

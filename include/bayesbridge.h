@@ -372,6 +372,70 @@ void bridge_regression_chains(double *betap, double *up, double *omegap, double 
                               const int *nchains);
 
 /*
+ * Posterior summaries of a chain batch without copying its traces.  The parameters of a chain
+ * are beta_1..beta_P, sig2, tau, alpha in that order (Q = P + 3; a known parameter is a
+ * constant trace).  Over the M samples a trace call returns (sample 0 is slot 0, the state the
+ * burn-in leaves), per chain and parameter:
+ *   mean, var          var unbiased (divisor M - 1);
+ *   acov[0..maxlag]    biased autocovariances (divisor M, centred at the chain's mean, as R's
+ *                      acf(type = "covariance")); lags >= M are 0;
+ *   hmean[2], hvar[2]  mean and unbiased variance of the first and of the last floor(M / 2)
+ *                      samples (the middle draw dropped when M is odd): the split of R-hat;
+ * and per chain `flags`, its error word.  These give the pooled mean and sd, split R-hat and
+ * coda's effective sample size.  0 <= maxlag <= 63, M >= 1.  The sums run in sample order on
+ * the device, a ring fill at a time behind the sweeps, so the results do not depend on the
+ * ring capacity, on ring wrap, on how the samples were split into calls or on the number of
+ * chains, and a non-finite sample affects its own chain and parameter only.
+ *
+ * bb_chains_summary_reset sizes and zeroes the accumulators of a batch for nsamp samples;
+ * bb_chains_summary_add adds ring slots [slot0, slot0 + count) (wrapping at the capacity) of
+ * every chain as the samples s0 .. s0 + count - 1, which must follow the samples added so far
+ * (it is enqueued behind the runs that wrote the slots and does not wait);
+ * bb_chains_summary_get returns the summaries once all nsamp samples are in: mean, var
+ * [K][Q], acov [K][Q][maxlag + 1], hmean, hvar [K][Q][2] (C order), flags [K]; an output
+ * pointer may be NULL.
+ */
+int bb_chains_summary_reset(bb_chains *b, int nsamp, int maxlag);
+int bb_chains_summary_add(bb_chains *b, int slot0, int count, int s0);
+int bb_chains_summary_get(bb_chains *b, double *mean, double *var, double *acov, double *hmean,
+                          double *hvar, int *flags);
+
+/*
+ * bridge_reg_stable_chains returning the summaries above instead of the traces: the chains
+ * are the same (one call key, chain c under (k0, k1 + c); the stream counter advances by K),
+ * on the same schedule and ring capacity.  meanp and varp are Q x K column-major, acovp
+ * (maxlag + 1) x Q x K, hmeanp and hvarp 2 x Q x K, flagsp K integers; `maxlag` is an input,
+ * then follow the inputs of bridge_reg_stable_chains in their order, `runtime` and `nchains`.
+ * Designs a chain batch does not take run their K chains one after another, each engine's
+ * ring reduced by the same kernel; a design that would be sharded by columns over several
+ * devices (bb_set_device_count) is refused with its outputs untouched.  nchains < 1, maxlag
+ * outside [0, 63] and M < 1 print an error (bb_last_error) and return before a key is taken
+ * or an output is written; an interrupted or failed run leaves the outputs as they were.
+ */
+void bridge_reg_stable_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
+                                      double *hvarp, int *flagsp, const int *maxlag,
+                                      const double *yp, const double *Xp,
+                                      const double *sig2_shape, const double *sig2_scale,
+                                      const double *nu_shape, const double *nu_rate,
+                                      const double *alpha_a, const double *alpha_b,
+                                      const double *true_sig2, const double *true_tau,
+                                      const double *true_alpha, const int *P, const int *N,
+                                      const int *M, const int *burn, double *runtime,
+                                      const int *ortho, const int *nchains);
+/* ... and of bridge_regression_chains (the triangle mixture) */
+void bridge_regression_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
+                                      double *hvarp, int *flagsp, const int *maxlag,
+                                      const double *yp, const double *Xp,
+                                      const double *sig2_shape, const double *sig2_scale,
+                                      const double *nu_shape, const double *nu_rate,
+                                      const double *alpha_a, const double *alpha_b,
+                                      const double *true_sig2, const double *true_tau,
+                                      const double *true_alpha, const int *P, const int *N,
+                                      const int *M, const int *burn, double *runtime,
+                                      const int *ortho, const int *betaburn, const int *use_hmc,
+                                      const int *nchains);
+
+/*
  * Shard group: `count` engines with cfg.rank = 0..count-1 and cfg.world = count, each
  * holding a column shard of one p > n chain.  Two kinds share the type:
  *   - bb_group_create: every member on ONE device, driven by one host thread, the per-sweep
@@ -622,6 +686,13 @@ int bb_bench_chol(int m, int reps, double *ms_factor, double *ms_solve,
 /* Gram C = Y diag(w) Y' (Y: n x k column-major) via the fp64 MFMA kernel;
  * C is n x n column-major, full symmetric result. */
 int bb_gram(double *C, const double *Y, const double *w, int n, int k);
+
+/* The trace-summary kernel alone (see bb_chains_summary_*): x is K chains of M samples of Q
+ * parameters, [K][M][Q] in C order, uploaded as trace rings (for Q > 3 the last three columns
+ * as the scalar rings of sig2, tau and alpha) and accumulated `chunk` samples at a time.
+ * Outputs as bb_chains_summary_get. */
+int bb_trace_summary(const double *x, int K, int M, int Q, int maxlag, int chunk, double *mean,
+                     double *var, double *acov, double *hmean, double *hvar);
 
 /* Microbenchmark of the Ozaki int8 GEMM alone on random residues (n x k, nsplit K splits, 0 =
  * automatic); dbg != 0 selects timing ablations (results then meaningless), except dbg = 999

@@ -14,6 +14,13 @@ k_tri_chains) into profiles/chains_tri_{c1,db}.json.  Its instances all give the
 there is no tuning key: the record's "instances" holds the kernel-only rate of every instance
 (ChainBatch.set_threads) at K = CUs, 2 CUs and 4 CUs, alternated within each round.
 
+--summary measures the summary mode (bridge_reg_*_chains_summary: each ring fill reduced on the
+device by bb_summary.hip k_trace_summary, nothing but the summaries copied) against the trace
+call of the same build at K = CUs and 4 CUs into profiles/chains_summary_{c1,db}.json
+(chains_summary_tri_* with --method tri): per K, alternated within each round, the summary
+call, the trace call, the kernel-only rate, and the share of the summary call's runtime that
+k_trace_summary takes (timed alone on a full ring of a ChainBatch, scaled to the call).
+
 Protocol: one warm-up call, then REPS rounds, each round visiting every K (and the
 single-chain bridge_reg_stb call) once, so slow drifts of the device hit every K alike; the
 median over rounds is reported with the min and max beside it.
@@ -22,6 +29,7 @@ median over rounds is reported with the min and max beside it.
   python tools/bench_chains.py --mode single --tree DIR   # bridge_reg_stb alone, from the
                                                           # checkout at DIR (A/B with a parent)
   python tools/bench_chains.py --method tri [--mode single --tree DIR]
+  python tools/bench_chains.py --summary [--method tri] [--designs c1]
 """
 import argparse
 import json
@@ -65,8 +73,12 @@ class Method:
         return (self.bb.bridge_reg_tri_chains if self.tri
                 else self.bb.bridge_reg_stb_chains)(y, X, **kw)
 
-    def config(self, n, p):
-        return self.bb.EngineConfig(n=n, p=p, trace_capacity=1, seed=SEED,
+    def summary(self, y, X, **kw):
+        return (self.bb.bridge_reg_tri_chains_summary if self.tri
+                else self.bb.bridge_reg_stb_chains_summary)(y, X, **kw)
+
+    def config(self, n, p, cap=1):
+        return self.bb.EngineConfig(n=n, p=p, trace_capacity=cap, seed=SEED,
                                     method=4 if self.tri else 0)
 
 
@@ -174,6 +186,68 @@ def bench_design(me, name, X, y, cus, args, Ks=None):
     return rec
 
 
+def summary_kernel_seconds(me, X, y, K, cap, nsamp, maxlag):
+    """Seconds k_trace_summary takes for nsamp samples of K chains: one full ring of `cap`
+    slots reduced alone (the sweeps that filled it already done), scaled to nsamp."""
+    n, p = X.shape
+    b = me.bb.ChainBatch(me.config(n, p, cap), K, X, y)
+    try:
+        b.init_state()
+        b.run(1, cap - 1, 1, 1, 1)
+        b.summary_reset(cap, maxlag)
+        b.summary_add(0, 1, 0)  # the first launch of the kernel is not timed
+        b.sync()
+        t0 = time.perf_counter()
+        b.summary_add(1, cap - 1, 1)
+        b.sync()
+        return (time.perf_counter() - t0) * nsamp / (cap - 1)
+    finally:
+        b.close()
+
+
+def bench_summary(me, name, X, y, cus, args):
+    """The summary call against the trace call, alternated within each round."""
+    bb = me.bb
+    Ks = [k for k in (args.chains or [cus, 4 * cus]) if k <= args.max_chains]
+    nsamp, burn = args.nsamp, args.burn
+    bb.set_seed(SEED)
+    me.summary(y, X, nsamp=200, nchains=2, burn=100)  # warm-up
+    me.chains(y, X, nsamp=200, nchains=2, burn=100)
+    keys = ("summary", "trace", "kernel", "summary_kernel_s")
+    v = {K: {k: [] for k in keys} for K in Ks}
+    cap, lag = {}, 0
+    for _ in range(args.reps):
+        for K in Ks:
+            bb.set_seed(SEED)
+            out = me.summary(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            v[K]["summary"].append(K * nsamp / out["runtime"])
+            cap[K], lag = bb.last_call_info()["trace_capacity"], out["maxlag"]
+            bb.set_seed(SEED)
+            out = me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            v[K]["trace"].append(K * nsamp / out["runtime"])
+            del out
+            v[K]["kernel"].append(kernel_rate(me, X, y, K, nsamp)[0])
+            v[K]["summary_kernel_s"].append(
+                summary_kernel_seconds(me, X, y, K, cap[K], nsamp, lag))
+    rows = []
+    for K in Ks:
+        s, t = spread(v[K]["summary"]), spread(v[K]["trace"])
+        ks = spread(v[K]["summary_kernel_s"])
+        rows.append({"chains": K, "ring_capacity": cap[K],
+                     "summary_call_sweeps_per_s": s, "trace_call_sweeps_per_s": t,
+                     "kernel_aggregate_sweeps_per_s": spread(v[K]["kernel"]),
+                     "summary_vs_trace": s["median"] / t["median"],
+                     "k_trace_summary_s": ks,
+                     "k_trace_summary_share": ks["median"] / (K * nsamp / s["median"])})
+    from bayesbridge_amd import _kernel_code
+
+    kname = "bb::k_trace_summary"
+    return {"design": name, "n": int(X.shape[0]), "p": int(X.shape[1]), "nsamp": nsamp,
+            "burn": burn, "reps": args.reps, "compute_units": cus, "maxlag": lag,
+            "method": "tri" if me.tri else "stable", "chains": rows,
+            "kernels": {kname: {"code_sha": _kernel_code.code_sha(kname)}}}
+
+
 def bench_single(me, args):
     """The single-chain call alone at both designs (one JSON line): the A/B against another
     checkout."""
@@ -204,6 +278,10 @@ def main():
                     help="KEY=VALUE,...: bb_set_tuning before measuring (A/B of a variant build)")
     ap.add_argument("--instances", type=lambda v: [int(t) for t in v.split(",")],
                     default=[512, 256, 128], help="triangle batch instances to compare (threads)")
+    ap.add_argument("--summary", action="store_true",
+                    help="the summary mode against the trace call (profiles/chains_summary_*)")
+    ap.add_argument("--chains", type=lambda v: [int(t) for t in v.split(",")], default=None,
+                    help="--summary: the batch sizes (default CUs,4 CUs)")
     ap.add_argument("--tag", default="", help="suffix of the output files' names")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
@@ -223,6 +301,22 @@ def main():
            else int(torch.cuda.get_device_properties(0).multi_processor_count))
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
+            continue
+        if args.summary:
+            rec = bench_summary(me, name, X, y, cus, args)
+            rec["source_sha"] = bb._build.source_sha()
+            stem = "chains_summary_tri_" if me.tri else "chains_summary_"
+            with open(os.path.join(args.out_dir, f"{stem}{name}{args.tag}.json"), "w") as f:
+                json.dump(rec, f, indent=1)
+                f.write("\n")
+            for r in rec["chains"]:
+                s, t = r["summary_call_sweeps_per_s"], r["trace_call_sweeps_per_s"]
+                print(f"{name} K={r['chains']:5d} summary {s['median']:.0f} sweeps/s "
+                      f"[{s['min']:.0f}, {s['max']:.0f}]  trace {t['median']:.0f} "
+                      f"[{t['min']:.0f}, {t['max']:.0f}]  kernel "
+                      f"{r['kernel_aggregate_sweeps_per_s']['median']:.0f}  x"
+                      f"{r['summary_vs_trace']:.2f}  k_trace_summary "
+                      f"{100 * r['k_trace_summary_share']:.2f} %", flush=True)
             continue
         rec = bench_design(me, name, X, y, cus, args)
         # the two-chains-per-CU instance (bb_set_tuning key 21) where it applies: K >= 2 CUs

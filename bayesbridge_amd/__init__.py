@@ -150,6 +150,7 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_engine_launch_counts.argtypes = [c.c_void_p, u64p, u64p]
     L.bb_kernel_instance.argtypes = [c.c_char_p, c.c_char_p, c.c_int]
     L.bb_engine_nid_mixed.argtypes = [c.c_void_p, u64p, u64p, _dp, _ip, _ip]
+    L.bb_engine_nid_beta32.argtypes = [c.c_void_p, u64p, _ip]
     L.bb_group_destroy.argtypes = [c.c_void_p]
     L.bb_group_init_state.argtypes = [c.c_void_p]
     L.bb_group_run.argtypes = [c.c_void_p, c.c_uint64, c.c_int, c.c_int, c.c_int, c.c_int]
@@ -1352,7 +1353,7 @@ class Engine:
 
     def nid_stats(self):
         """Near-identity (Chebyshev) solve counters: dict(cheb_sweeps,
-        products, chol_sweeps, eps, mode) -- mode/eps of the latest sweep, -1 when the engine
+        products, chol_sweeps, eps, mode, beta32_sweeps) -- mode/eps of the latest sweep, -1 when the engine
         has no near-identity path."""
         a, b, c = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_ulonglong()
         eps, mode = ctypes.c_double(), ctypes.c_int()
@@ -1362,18 +1363,28 @@ class Engine:
         lam, kmax = ctypes.c_double(), ctypes.c_int()
         library().bb_engine_nid_bound(self._h, ctypes.byref(lam), ctypes.byref(kmax))
         return dict(cheb_sweeps=a.value, products=b.value, chol_sweeps=c.value, eps=eps.value,
-                    mode=mode.value, lambda_x=lam.value, kmax=kmax.value)
+                    mode=mode.value, lambda_x=lam.value, kmax=kmax.value,
+                    beta32_sweeps=self._beta32()[0])
+
+    def _beta32(self):
+        """(sweeps that took the fp32 beta pass; whether the latest did)"""
+        a, f = ctypes.c_ulonglong(), ctypes.c_int()
+        _check(library().bb_engine_nid_beta32(self._h, ctypes.byref(a), ctypes.byref(f)),
+               "bb_engine_nid_beta32")
+        return a.value, bool(f.value)
 
     def nid_mixed(self):
         """The mixed-precision plan: dict(mixed_sweeps, products32 (fp32
-        E-apply passes), eta and k2 of the latest sweep, holds_x32)."""
+        E-apply passes), eta and k2 of the latest sweep, holds_x32, beta32_sweeps and
+        beta32: sweeps that took the fp32 beta pass of s6.7, whether the latest did)."""
         a, b = ctypes.c_ulonglong(), ctypes.c_ulonglong()
         eta, k2, hx = ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
         _check(library().bb_engine_nid_mixed(self._h, ctypes.byref(a), ctypes.byref(b),
                                              ctypes.byref(eta), ctypes.byref(k2),
                                              ctypes.byref(hx)), "bb_engine_nid_mixed")
+        n32, last32 = self._beta32()
         return dict(mixed_sweeps=a.value, products32=b.value, eta=eta.value, k2=k2.value,
-                    holds_x32=bool(hx.value))
+                    holds_x32=bool(hx.value), beta32_sweeps=n32, beta32=last32)
 
     def launch_counts(self):
         """Woodbury lambda launches since creation: dict(lambda_xu = fused with the X u stream

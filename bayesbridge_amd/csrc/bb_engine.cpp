@@ -116,6 +116,11 @@ int g_nid_poll = 1;
 // (1, the default); 2: unsharded, the launch's last stream workgroup reduces and decides too;
 // 0: k_nid_sums + k_nid_reduce after the launch
 int g_nid_fold = 1;
+// bb_set_tuning key 24: beta of a certified near-identity sweep from the banked X'x dots and one
+// pass over the fp32 copy of X (unsharded dense engines holding X32): 0 never,
+// 1 where certified and the cost model says the halved pass pays (the default), 2 wherever
+// certified (tests at small shapes)
+int g_nid_b32 = 1;
 // bb_set_tuning key 21: chain batches of at least 2 x CUs chains created from now on run the
 // 256-thread instance, two chains per CU (faster in aggregate there; its chains
 // match the oracle but are not bit for bit those of sequential calls)
@@ -192,6 +197,11 @@ struct bb_engine {
     float *X32 = nullptr;
     double *ch_b = nullptr;
     int nid_k2 = 0;
+    // the fp32 beta pass (engines holding X32): the banked dots X_j' x_{K-1}
+    // (p_loc), the mixed plan's correction and the summed X u (n_pad), and whether the latest
+    // decision set NidState::b32
+    double *gb = nullptr, *ch_c = nullptr, *ch_xu = nullptr;
+    bool nid_b32 = false;
     double nid_cost[3] = {0.0, 0.0, 0.0};  // NidState c64, c32, cstep (s)
     int ea_parts = 1;
     int nid_kmax = 0;  // iterations beyond which the Gram + Cholesky path is cheaper (model)
@@ -297,6 +307,18 @@ struct bb_engine {
     bool mixed_ok() const {
         return X32 != nullptr && g_nid_mixed && !sharded() && !group_member && dense();
     }
+    // the sweep's decision may set b32: the engine can run the mixed plan (so it holds X32 and
+    // keeps b), decides under the synchronous protocol (the host learns the flag with the
+    // decision) and has the fused beta pass's shape
+    bool b32_ok() const { return gb != nullptr && g_nid_b32 && mixed_ok() && nid_sync(); }
+    int allow_mask() const {
+        return (mixed_ok() ? kAllowMixed : 0) |
+               (b32_ok() ? kAllowBeta32 | (g_nid_b32 == 2 ? kBeta32AnyCost : 0) : 0);
+    }
+    double *bank() const { return b32_ok() ? gb : nullptr; }
+    Beta32Vecs b32_vecs() const {
+        return b32_ok() ? Beta32Vecs{ch_c, ch_b, ch_xu, xb_part} : Beta32Vecs{};
+    }
     // the exchanged vectors are single n-vectors on a shard; an unsharded engine in the
     // synchronous mode reads the partials directly
     bool nid_vec() const { return sharded() || sparse(); }
@@ -400,12 +422,12 @@ struct bb_engine {
         else if (folded == 1)
             launch_nid_reduce(stream, nid_wg, nstream, sc, nid, nid_red,
                               std::min(g_nid_kmax, nid_kmax), eps_dev + kNidRing,
-                              mixed_ok() ? 1 : 0, ++nid_dseq);
+                              allow_mask(), ++nid_dseq);
         else if (sharded())
             launch_nid_sums(stream, D, cn, p_loc, sc, nid, 0, 0, 0, nid_wg, nid_red, nullptr);
         else
             launch_nid_sums_decide(stream, D, cn, p_loc, sc, nid, std::min(g_nid_kmax, nid_kmax),
-                                   nid_wg, nid_red, eps_dev + kNidRing, mixed_ok() ? 1 : 0,
+                                   nid_wg, nid_red, eps_dev + kNidRing, allow_mask(),
                                    ++nid_dseq);
     }
     // the decision from the reduced sums (identical on every rank), then wait for it
@@ -428,6 +450,8 @@ struct bb_engine {
             mode = (int)((volatile double *)eps_host)[kNidRing + 1];
             k2 = (int)((volatile double *)eps_host)[kNidRing + 2];
         }
+        nid_b32 = b32_ok() && (k2 & 128) != 0;  // b32 rides in bit 7 of k2 (nid_finish)
+        k2 &= 127;
         nid_k2 = mixed_ok() ? k2 : 0;
         nid_only = mode > 0;
         nid_last = mode;
@@ -497,20 +521,22 @@ struct bb_engine {
         else
             launch_cheb_init(stream, nid_xu, xu_fused ? xu_fused : ea_parts, n, n_pad, y, sc,
                              cfg.seed, cfg.stream, t, nid, w, ch_r, ch_d,
-                             mixed_ok() ? ch_b : nullptr);
+                             mixed_ok() ? ch_b : nullptr, b32_ok() ? ch_xu : nullptr);
     }
     // the mixed plan's residual pass, restart and correction solve (k2 iterates), after the
     // first solve's products
     void nidx_mixed_tail(int k2) {
+        const Beta32Vecs bv = b32_vecs();
         mark(PH_EAPPLY);
-        launch_eapply(stream, X, n_pad, n_pad, p_loc, D, w, nid, 0, ea_part, X32, 2);
+        launch_eapply(stream, X, n_pad, n_pad, p_loc, D, w, nid, 0, ea_part, X32, 2, bank());
         mark(PH_NID);
-        launch_cheb_restart(stream, ea_part, ea_parts, n_pad, sc, nid, ch_b, w, ch_r, ch_d);
+        launch_cheb_restart(stream, ea_part, ea_parts, n_pad, sc, nid, ch_b, w, ch_r, ch_d, &bv);
         for (int j = 1; j < k2; ++j) {
             mark(PH_EAPPLY);
             launch_eapply(stream, X, n_pad, n_pad, p_loc, D, ch_d, nid, j, ea_part, X32, 3);
             mark(PH_NID);
-            launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d, 2);
+            launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d, 2,
+                             &bv);
         }
     }
     // this shard's E d of step j into nid_sum (exchanged: n_pad)
@@ -521,7 +547,7 @@ struct bb_engine {
                              spd.rval, p_loc, n_pad, D, ch_d, nid, j, sp_s, nid_sum);
         } else {
             launch_eapply(stream, X, n_pad, n_pad, p_loc, D, ch_d, nid, j, ea_part,
-                          mixed_ok() ? X32 : nullptr);
+                          mixed_ok() ? X32 : nullptr, 0, bank());
             if (nid_vec()) launch_part_sum(stream, ea_part, ea_parts, n_pad, nid_sum);
         }
     }
@@ -529,8 +555,10 @@ struct bb_engine {
         mark(PH_NID);
         if (nid_vec())
             launch_cheb_step(stream, nid_sum, 1, n_pad, sc, nid, j, w, ch_r, ch_d);
-        else
-            launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d);
+        else {
+            const Beta32Vecs bv = b32_vecs();
+            launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d, 1, &bv);
+        }
     }
     // X beta of the current beta into the partials k_pre sums next
     void xbeta() {
@@ -621,7 +649,7 @@ struct bb_engine {
                     fold.cnt = lam_sync + lambda_xs_sync_words(p_pad);
                     fold.decide = (!sharded() && g_nid_fold == 2) ? 1 : 0;
                     fold.k_launched = std::min(g_nid_kmax, nid_kmax);
-                    fold.allow_mixed = mixed_ok() ? 1 : 0;
+                    fold.allow_mixed = allow_mask();
                     fold.nid = nid;
                     fold.red = nid_red;
                     fold.host2 = eps_dev + kNidRing;
@@ -638,6 +666,7 @@ struct bb_engine {
                               cfg.stream, t, LAMBDA_WOODBURY, group, lam, D, u, trl, err);
             ++(xu_fused ? n_lambda_xu : n_lambda_alone);
             nid_only = false;
+            nid_b32 = false;
             if (sync) {
                 // a shard: the bound sums now, the path after their exchange (solve_schedule)
                 nid_kl = 0;
@@ -717,7 +746,14 @@ struct bb_engine {
             launch_sp_beta(stream, spd.colptr, spd.rowidx, spd.cval, p_loc, w, u, D, sc, beta, trb);
         } else if (dense()) {
             mark(PH_BETA);
-            if (beta_xb_supported(n_pad)) {
+            if (nid_only && nid_b32) {
+                // a b32 sweep: beta from the banked dots and one pass over X32; its X beta was
+                // written by the solve's last step, the single partial k_pre sums next
+                launch_beta_woodbury32(stream, X32, n_pad, n_pad, ch_d, ch_c, gb, u, D, sc, nid,
+                                       p_loc, beta, trb);
+                nparts = 1;
+                xb_fused = true;
+            } else if (beta_xb_supported(n_pad)) {
                 // beta and the X beta partials of the next sweep in one pass over X
                 launch_beta_woodbury_xb(stream, X, n_pad, n_pad, w, u, D, sc, p_loc, beta, trb,
                                         xb_part);
@@ -1339,6 +1375,14 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
                     } else {
                         o.push_back(x32);
                         e->X32 = (float *)x32;
+                        if (beta_xb_supported(n_pad)) {  // the fp32 beta pass's vectors
+                            e->gb = dalloc<double>(p_pad, o);
+                            e->ch_c = dalloc<double>(n_pad, o);
+                            e->ch_xu = dalloc<double>(n_pad, o);
+                            HIPCHECK(hipMemsetAsync(e->gb, 0, sizeof(double) * p_pad, e->stream));
+                            HIPCHECK(hipMemsetAsync(e->ch_c, 0, sizeof(double) * n_pad, e->stream));
+                            HIPCHECK(hipMemsetAsync(e->ch_xu, 0, sizeof(double) * n_pad, e->stream));
+                        }
                     }
                 }
             }
@@ -2101,6 +2145,18 @@ int bb_engine_nid_mixed(bb_engine *e, unsigned long long *mixed_sweeps,
         if (eta) *eta = h.eta;
         if (k2) *k2 = h.k2;
         if (holds_x32) *holds_x32 = e->X32 != nullptr;
+    });
+}
+
+int bb_engine_nid_beta32(bb_engine *e, unsigned long long *beta32_sweeps, int *b32) {
+    return guarded([&] {
+        NidState h{};
+        if (e->nid) {
+            HIPCHECK(hipMemcpyAsync(&h, e->nid, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(hipStreamSynchronize(e->stream));
+        }
+        if (beta32_sweeps) *beta32_sweeps = h.n_beta32;
+        if (b32) *b32 = h.b32;
     });
 }
 
@@ -3339,7 +3395,8 @@ int bb_set_tuning(int key, int value) {
                  {6, &g_nid_kmax, 64},  {7, &g_lam_xu, 3},     {8, &g_nid_sync, 2},
                  {9, &g_shard_proto, 1}, {10, &g_nid_mixed, 1}, {11, &g_nid_poll, 1},
                  {12, &g_rs_xcd, 1},    {13, &g_lam_wave, 1},  {15, &g_lam_lend, 1},
-                 {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1}};
+                 {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1},
+                 {24, &g_nid_b32, 2}};
     for (const auto &k : kKeys)
         if (k.key == key) {
             const int old = *k.var;

@@ -58,8 +58,18 @@ struct NidState {
     // the plans' cost model (s, set at setup from the shape): an fp64 / fp32 pass over X and
     // the per-iterate step launch
     double c64, c32, cstep;
+    // b32: this sweep forms beta from the banked X'x dots and one fp32 pass over X (DESIGN.md
+    // s6.7; the host reads it with the decision and launches k_beta_wb32, which checks it,
+    // in place of k_beta_wb_xb); n_beta32 counts such sweeps
+    int b32;
+    unsigned long long n_beta32;
 };
 constexpr double kNidTol = 1.3877787807814457e-17;  // 2^-56: bound on the relative error
+// 2^-26: the largest |w_s| / |w| at which the part w_s of w may be dotted against fl32(X) in
+// the beta pass.  |x_j - fl32(x_j)| <= 2^-24 |x_j| entrywise, so the dot moves
+// by at most 2^-24 2^-26 |x_j| |w| = 2^-50 |x_j| |w|, below sqrt(n) 2^-53 |x_j| |w|, the expected
+// rounding of the fp64 dot product X_j' w itself, for every n >= 64.
+constexpr double kBeta32Tol = 1.4901161193847656e-08;
 
 // Chebyshev scalars of the interval [1, 1 + eps]
 struct ChebConst {
@@ -89,6 +99,19 @@ __host__ __device__ inline int cheb_iterations(double eps, int kmax, double tol)
     return 0;
 }
 
+// sqrt(1 + eps) / T_k(sigma1): the bound on |w - x_k| / |w| that cheb_iterations tests, by the
+// same recurrence (k >= 1, eps > 0)
+__host__ __device__ inline double cheb_bound_at(double eps, int k) {
+    const ChebConst c = cheb_const(eps);
+    double tm1 = 1.0, tk = c.sigma1;  // T_0, T_1
+    for (int i = 1; i < k; ++i) {
+        const double tn = 2.0 * c.sigma1 * tk - tm1;
+        tm1 = tk;
+        tk = tn;
+    }
+    return sqrt(1.0 + eps) / tk;
+}
+
 // a kernel of the Gram + Cholesky path: skip it when the sweep took the Chebyshev path
 __device__ __forceinline__ bool gated(const int *gate) { return gate && *gate != 0; }
 
@@ -104,8 +127,12 @@ bool eapply_supported(int n_pad);        // dense E-apply register tiling covers
 // (wg_part, G x (kNidTS + 1)) reduced in order into red (kNidTS + 2: [S_k | trace | Lambda]);
 // decide != 0: the unsharded decision at once (eps into the host-mapped eps_host); a shard
 // exchanges red, then launch_nid_decide_from (host2 = host-mapped [eps, mode, k2, tag]; tag_seq
-// != 0: the tag word (seq << 16 | mode << 8 | k2) the host polls for the decision)
+// != 0: the tag word (seq << 16 | mode << 8 | b32 << 7 | k2) the host polls for the decision;
+// host2[2] = k2 + 128 b32)
 constexpr int kNidTS = 32;
+// the decision's allow_mixed mask: the mixed plan may be chosen; the sweep may take the fp32
+// beta pass (NidState::b32); ... whatever the cost model says (bb_set_tuning key 24 = 2)
+constexpr int kAllowMixed = 1, kAllowBeta32 = 2, kBeta32AnyCost = 4;
 int nid_sum_groups(int p_loc);
 void launch_nid_sums(hipStream_t s, const double *D, const double *cn, int p_loc,
                      const DevScalars *sc, NidState *nid, int k_launched, int allow, int decide,
@@ -139,28 +166,42 @@ void launch_nid_decide_from(hipStream_t s, const double *red, const DevScalars *
                             unsigned long long tag_seq = 0);
 void launch_nid_xu(hipStream_t s, const double *X, int ldx, const double *u, int ncols,
                    int n_pad, const NidState *nid, double *part);
-// b (optional): the right-hand side, kept for the mixed plan's residual pass
+// b (optional): the right-hand side, kept for the mixed plan's residual pass; xu (optional):
+// the summed X u, kept for the X beta of a b32 sweep (Beta32Vecs)
 void launch_cheb_init(hipStream_t s, const double *xu_part, int nparts, int n, int n_pad,
                       const double *y, const DevScalars *sc, uint64_t k0, uint64_t k1,
                       uint64_t t, const NidState *nid, double *x, double *r, double *d,
-                      double *b = nullptr);
+                      double *b = nullptr, double *xu = nullptr);
+// The n-vectors of an engine that may take the fp32 beta pass.  The restart
+// writes the mixed plan's correction into c and its steps add to it (c = w - x0, accumulated,
+// not formed as a difference).  On a b32 sweep the solve's last step (or restart) writes
+//   X beta = X u + sig (b - w)      (M w = b - rho, |rho| <= 2^-56 |w|)
+// into xb, the single partial k_pre sums next sweep.
+struct Beta32Vecs {
+    double *c = nullptr;
+    const double *b = nullptr, *xu = nullptr;
+    double *xb = nullptr;
+};
 // phase 1: step j of the first solve (runs if mode > j); phase 2: step j of the mixed plan's
 // correction solve (runs if k2 > j)
 void launch_cheb_step(hipStream_t s, const double *part, int nparts, int n_pad,
                       const DevScalars *sc, const NidState *nid, int j, double *x, double *r,
-                      double *d, int phase = 1);
+                      double *d, int phase = 1, const Beta32Vecs *bv = nullptr);
 // the mixed plan's restart: r = b - x - (E x) / sig2 from the fp64 residual pass's partials,
 // d = r / theta, x += d (runs if k2 > 0 and mode > 0)
 void launch_cheb_restart(hipStream_t s, const double *part, int nparts, int n_pad,
                          const DevScalars *sc, const NidState *nid, const double *b, double *x,
-                         double *r, double *d);
+                         double *r, double *d, const Beta32Vecs *bv = nullptr);
 // One pass over X: part = X D X' v partials.  kind 0: product j of the first solve (runs if
 // mode > j; streams X32 when the sweep took the mixed plan and X32 is given); 2: the mixed
 // plan's fp64 residual pass (v = the iterate; runs if k2 > 0 and mode > 0); 3: product j of
 // the correction solve (X32; runs if k2 > j)
+// gb (optional; an engine that may take the fp32 beta pass): on a b32 sweep the passes that
+// stream fp64 X bank their per-column dots X_j' v there -- kind 0 writes them at j = 1 and adds
+// to them at j > 1 (the sum is X_j' x_{K-1}), kind 2 writes X_j' x0 (one writer per column)
 void launch_eapply(hipStream_t s, const double *X, int ldx, int n_pad, int p_loc,
                    const double *D, const double *v, const NidState *nid, int j, double *part,
-                   const float *X32 = nullptr, int kind = 0);
+                   const float *X32 = nullptr, int kind = 0, double *gb = nullptr);
 // X32 = X rounded to fp32 (n_pad x ncols, ld ldx); *bad = 1 if an entry is outside the range
 // where the rounding error is <= 2^-24 |x| (|x| > 2^126 or 0 < |x| < 2^-125)
 void launch_cast_f32(hipStream_t s, const double *X, int ldx, int n_pad, int ncols, float *X32,
@@ -324,6 +365,13 @@ bool beta_xb_supported(int n_pad);
 void launch_beta_woodbury_xb(hipStream_t s, const double *X, int ldx, int n_pad, const double *w,
                              const double *u, const double *D, const DevScalars *sc, int p_loc,
                              double *beta, double *beta_trace, double *part);
+// beta of a b32 sweep (beta_xb_supported(n_pad)): beta_j = u_j + D_j (gb_j +
+// X32_j' w_s) / sig with w_s = wc on a mixed sweep (k2 > 0), else wd; one pass over the fp32
+// copy of X, no X beta partials.  The kernel returns at once unless nid->b32 is set.
+void launch_beta_woodbury32(hipStream_t s, const float *X32, int ldx, int n_pad, const double *wd,
+                            const double *wc, const double *gb, const double *u, const double *D,
+                            const DevScalars *sc, const NidState *nid, int p_loc, double *beta,
+                            double *beta_trace);
 
 // Build the 2-RHS backward-solve input [U'^-1 c | z] (chol path).
 void launch_chol_rhs(hipStream_t s, const double *A, int lda, int rhs_col, int p, int p_pad,

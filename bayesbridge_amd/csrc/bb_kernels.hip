@@ -3264,6 +3264,94 @@ void launch_beta_woodbury_xb(hipStream_t s, const double *X, int ldx, int n_pad,
     }
 }
 
+// beta of a b32 sweep: beta_j = u_j + D_j (gb_j + X32_j' w_s) / sig, where gb_j
+// is the banked fp64 dot of column j with everything but the solve's last, small part w_s
+// (d_{K-1} of an fp64 sweep, the correction c of a mixed one: |w_s| <= 2^-26 |w| certified by
+// the decision), so the pass streams the fp32 copy of X -- half the bytes -- and the fp32
+// rounding moves the dot by less than its own fp64 rounding.  k_beta_wb_xb's structure (a wave
+// per column, three column buffers in flight, raw loads first, conversion after -- exact, the
+// arithmetic is fp64) without the X beta axpy: X beta comes from the solve's n-vectors
+// (Beta32Vecs).  Returns at once unless the device set b32.  NR = n_pad / 128 <= 16.
+template <int NR>
+__global__ __launch_bounds__(64 * kBxbWaves, 1) void k_beta_wb32(
+    const float *__restrict__ X32, int ldx, const double *__restrict__ wd,
+    const double *__restrict__ wc, const double *__restrict__ gb, const double *__restrict__ u,
+    const double *__restrict__ D, const DevScalars *sc, const NidState *nid, int p_loc,
+    double *__restrict__ beta, double *__restrict__ trace) {
+    if (!nid->b32) return;
+    typedef float v2f_ __attribute__((ext_vector_type(2)));
+    __shared__ double ws[NR * 128];
+    const double *__restrict__ wsm = nid->k2 > 0 ? wc : wd;
+    for (int i = threadIdx.x; i < NR * 128; i += 64 * kBxbWaves) ws[i] = wsm[i];
+    __syncthreads();
+    const double sig = sqrt(sc->sig2);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int nw = gridDim.x * kBxbWaves;
+    // a buffer holds column j and its (u_j, D_j, gb_j), every load issued together (past the
+    // end the last column is re-read: branch-free, so the waits stay counted)
+    struct Col {
+        double u, D, g;
+    };
+    auto load = [&](int j, v2f_ (&xv)[NR], Col &cj) {
+        const int jj = min(j, p_loc - 1);
+        const float *col = X32 + (size_t)jj * ldx + 2 * lane;
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+            xv[i] = __builtin_nontemporal_load((const v2f_ *)(col + 128 * i));
+        cj = Col{u[jj], D[jj], gb[jj]};
+    };
+    auto step = [&](int j, v2f_ (&xc)[NR], Col &cj) {
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const double2 wv = *(const double2 *)&ws[128 * i + 2 * lane];
+            s0 = __builtin_fma((double)xc[i].x, wv.x, s0);
+            s1 = __builtin_fma((double)xc[i].y, wv.y, s1);
+        }
+        const double s = wave_allsum(s0 + s1);
+        if (lane == 0) {
+            const double bj = cj.u + cj.D * (cj.g + s) / sig;
+            beta[j] = bj;
+            if (trace) trace[j] = bj;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        load(j + 3 * nw, xc, cj);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    v2f_ xa[NR], xb[NR], xcol[NR];
+    Col ca, cb, cc;
+    int j = blockIdx.x * kBxbWaves + wid;
+    load(j, xa, ca);
+    load(j + nw, xb, cb);
+    load(j + 2 * nw, xcol, cc);
+    for (; j + 2 * nw < p_loc; j += 3 * nw) {
+        step(j, xa, ca);
+        step(j + nw, xb, cb);
+        step(j + 2 * nw, xcol, cc);
+    }
+    if (j < p_loc) step(j, xa, ca);
+    if (j + nw < p_loc) step(j + nw, xb, cb);
+}
+
+void launch_beta_woodbury32(hipStream_t s, const float *X32, int ldx, int n_pad, const double *wd,
+                            const double *wc, const double *gb, const double *u, const double *D,
+                            const DevScalars *sc, const NidState *nid, int p_loc, double *beta,
+                            double *beta_trace) {
+    const int g = beta_xb_parts(p_loc);
+    switch (n_pad / 128) {
+#define BW32(NR)                                                                            \
+    case NR:                                                                                \
+        note_launch(KF_BETA, (const void *)k_beta_wb32<NR>);                                \
+        k_beta_wb32<NR><<<g, 64 * kBxbWaves, 0, s>>>(X32, ldx, wd, wc, gb, u, D, sc, nid,  \
+                                                     p_loc, beta, beta_trace);             \
+        break;
+        BW32(1) BW32(2) BW32(3) BW32(4) BW32(5) BW32(6) BW32(7) BW32(8)
+        BW32(9) BW32(10) BW32(11) BW32(12) BW32(13) BW32(14) BW32(15) BW32(16)
+#undef BW32
+        default: break;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_chol_rhs(const double *A, int lda, int rhs_col, int p,
                                                   int p_pad, Key key, uint64_t t, double *Y2) {
     const int r = blockIdx.x * 256 + threadIdx.x;

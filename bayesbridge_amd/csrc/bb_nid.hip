@@ -94,10 +94,16 @@ __device__ __forceinline__ double shard_threshold(double tau2, int k) {
 // sigma1), overflow giving t_k = 0; a 1e-12 relative margin covers the closed form's rounding),
 // lane k1 - 1 finds its least k2 by a binary search (t_k2 by shuffle), then the cheapest
 // (cost, k1) by a wave minimum: ~1 us, against ~40 us for the same search on one thread.
+// bsave: what the sweep's beta pass saves when it may stream the fp32 copy
+// (c64 - c32; 0 when the pass is not allowed).  A plan whose first solve is within kBeta32Tol
+// earns it, and so does a certified fp64 plan (cost_fp64 arrives with it taken off), so the
+// search prefers, among plans of like cost, the one that halves the beta pass as well.
 __device__ void nid_plan_mixed(double eps, double tr, int kcap, double cost_fp64,
-                               const NidState *nid, int &K1, int &K2, double &eta, double &e2) {
+                               const NidState *nid, int &K1, int &K2, double &eta, double &e2,
+                               double &err1_out, double bsave) {
     const int lane = threadIdx.x & 63;
     K1 = K2 = 0;
+    err1_out = HUGE_VAL;
     eta = (2.0 * kU32 * sqrt(tr * eps) + kU32 * kU32 * tr) * (1.0 + 1e-6);
     e2 = eps + eta;
     if (!(e2 < 1e300) || kcap < 1) return;
@@ -107,7 +113,7 @@ __device__ void nid_plan_mixed(double eps, double tr, int kcap, double cost_fp64
     const double tk = (lane + 1 <= kmax) ? sqrt(1.0 + e2) / cosh((lane + 1) * ac) * (1.0 + 1e-12)
                                          : HUGE_VAL;
     const double step32 = nid->c32 + nid->cstep, step64 = nid->c64 + nid->cstep;
-    const double cap = fmin(cost_fp64, (kcap - 1) * step64);
+    const double cap = (kcap - 1) * step64;
     const int k1 = lane + 1;
     const double err1 = eta + tk * (1.0 + eta);
     const double need = kNidTol / err1;
@@ -130,6 +136,8 @@ __device__ void nid_plan_mixed(double eps, double tr, int kcap, double cost_fp64
                       ? (k1 - 1) * step32 + step64 + (k2 - 1) * step32
                       : HUGE_VAL;
     if (!(cost < cap * (1.0 - 1e-9))) cost = HUGE_VAL;
+    if (err1 * (1.0 + 1e-6) <= kBeta32Tol) cost -= bsave;
+    if (!(cost < cost_fp64 * (1.0 - 1e-9))) cost = HUGE_VAL;
     // wave minimum of (cost, k1): deterministic, ties to the smaller k1
     double bc = cost;
     int bk1 = k1, bk2 = k2;
@@ -143,9 +151,12 @@ __device__ void nid_plan_mixed(double eps, double tr, int kcap, double cost_fp64
             bk2 = ok2;
         }
     }
+    // |x0 - w| / |w| of the chosen first solve: the bound on the correction
+    const double be = __shfl(err1, (bk1 - 1) & 63, 64);
     if (bc < HUGE_VAL) {
         K1 = bk1;
         K2 = bk2;
+        err1_out = be;
     }
 }
 
@@ -173,7 +184,14 @@ __device__ __forceinline__ double round_up_12(double x) {
 }
 
 // eps from the least bound, the iteration count K and the sweep's mode: called by the 64
-// lanes of one wave (every lane computes the same values; lane 0 writes them)
+// lanes of one wave (every lane computes the same values; lane 0 writes them).
+// allow_mixed is a mask: kAllowMixed the mixed plan may be chosen, kAllowBeta32 the sweep may
+// form beta from the banked dots and one fp32 pass (the flag b32),
+// kBeta32AnyCost: ... even where the cost model says the pass is launch-bound (key 24 = 2).
+// b32 is set when the part of w that was not dotted against fp64 X is certified small:
+//   fp64 plan, K >= 2: w - x_{K-1} = d_{K-1}, |d_{K-1}| <= (t_K + t_{K-1}) |w|;
+//   mixed plan: w - x0 = c, |c| <= err1 |w| (nid_plan_mixed's bound on the first solve);
+// bound (1 + 1e-6) <= kBeta32Tol, and the saving c64 - c32 exceeds a launch (cstep).
 __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launched, int allow,
                            NidState *nid, double *eps_host, double *mode_host,
                            int allow_mixed = 0, double *k2_host = nullptr,
@@ -189,14 +207,19 @@ __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launch
     int K = cheb_iterations(eps, k_launched, kNidTol);
     if (g_dev_nid_force_k > 0) K = g_dev_nid_force_k < k_launched ? g_dev_nid_force_k : k_launched;
     int mode = (allow && K > 0) ? K : 0, k2 = 0;
-    double ecb = eps, eta = 0.0;
+    double ecb = eps, eta = 0.0, err1 = HUGE_VAL;
+    const bool b32_pays = (allow_mixed & kAllowBeta32) && g_dev_nid_force_k == 0 &&
+                          ((allow_mixed & kBeta32AnyCost) || nid->c64 - nid->c32 > nid->cstep);
+    const double bsave = b32_pays ? nid->c64 - nid->c32 : 0.0;
     // a mixed plan costs at least one fp64 pass (k1 = k2 = 1): never below K <= 2's
-    if (allow && allow_mixed && g_dev_nid_force_k == 0 && (K == 0 || K > 2)) {
+    if (allow && (allow_mixed & kAllowMixed) && g_dev_nid_force_k == 0 && (K == 0 || K > 2)) {
         const double tr = round_up_12(red[kNidTS] / sc->sig2 * (1.0 + 1e-6));
         int k1m, k2m;
         double e2;
-        nid_plan_mixed(eps, tr, k_launched, K > 0 ? (K - 1) * (nid->c64 + nid->cstep) : HUGE_VAL,
-                       nid, k1m, k2m, eta, e2);
+        // (K > 2 here: a certified fp64 plan always earns bsave, see the b32 rule below)
+        nid_plan_mixed(eps, tr, k_launched,
+                       K > 0 ? (K - 1) * (nid->c64 + nid->cstep) - bsave : HUGE_VAL, nid, k1m,
+                       k2m, eta, e2, err1, bsave);
         if (k2m > 0) {
             mode = k1m;
             k2 = k2m;
@@ -206,9 +229,20 @@ __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launch
         }
     }
     if ((threadIdx.x & 63) != 0) return;
+    int b32 = 0;
+    if (b32_pays && mode > 0) {
+        double bound = HUGE_VAL;
+        if (k2 > 0)
+            bound = err1;
+        else if (mode >= 2 && eps > 0.0)
+            bound = cheb_bound_at(eps, mode) + cheb_bound_at(eps, mode - 1);
+        b32 = bound * (1.0 + 1e-6) <= kBeta32Tol;
+    }
     nid->eps = eps;
     nid->mode = mode;
     nid->k2 = k2;
+    nid->b32 = b32;
+    nid->n_beta32 += (unsigned long long)b32;
     nid->eta = eta;
     const ChebConst c = cheb_const(ecb);
     nid->theta = c.theta;
@@ -227,13 +261,14 @@ __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launch
     }
     if (eps_host) *eps_host = eps;  // host-mapped: the launch hint / the shard's decision
     if (mode_host) *mode_host = (double)mode;
-    if (k2_host) *k2_host = (double)k2;
+    if (k2_host) *k2_host = (double)(k2 + 128 * b32);  // k2 <= 64: b32 rides in bit 7
     // the host's wake-up word (host2[3], coherent host memory): the decision's sequence number,
     // mode and k2 in one 64-bit store, so the host polls it instead of waiting on an event
     // (an event marker in the stream cost ~6 us of idle device per sweep)
     if (tag_seq && mode_host)
         __hip_atomic_store((unsigned long long *)(mode_host + 2),
-                           (tag_seq << 16) | ((unsigned long long)mode << 8) | (unsigned)k2,
+                           (tag_seq << 16) | ((unsigned long long)mode << 8) |
+                               (unsigned)(k2 | (b32 << 7)),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -431,7 +466,7 @@ template <int RW>
 __global__ __launch_bounds__(kRsThreads) void k_cheb_init(
     const double *__restrict__ xu_part, int nparts, int n, int n_pad,
     const double *__restrict__ y, const DevScalars *sc, Key key, uint64_t t, const NidState *nid,
-    double *x, double *r, double *d, double *b, int xcd) {
+    double *x, double *r, double *d, double *b, double *xu_out, int xcd) {
     if (nid->mode == 0) return;
     const int i = rs_block(xcd) * RW + (int)threadIdx.x;
     const double xu = part_rowsum_rw<RW>(xu_part, nparts, n_pad, rs_block(xcd) * RW);
@@ -447,14 +482,24 @@ __global__ __launch_bounds__(kRsThreads) void k_cheb_init(
     d[i] = d0;
     x[i] = d0;
     if (b) b[i] = rhs;
+    if (xu_out) xu_out[i] = xu;
+}
+
+// X beta of a b32 sweep from the n-vectors (Beta32Vecs): row i of the single partial
+__device__ __forceinline__ void beta32_xb(const Beta32Vecs &bv, const DevScalars *sc, int i,
+                                          double w) {
+    bv.xb[i] = bv.xu[i] + sqrt(sc->sig2) * (bv.b[i] - w);
 }
 
 // Chebyshev step j (1 <= j <= K - 1): q = d + (sum of the E-apply partials) / sig2,
 // r_j = r_{j-1} - q, d_j = rho_j rho_{j-1} d_{j-1} + (2 rho_j / delta) r_j, x_{j+1} = x_j + d_j.
+// bv (an engine that may take the fp32 beta pass): a phase-2 step adds d_j to the correction;
+// the solve's last step writes the X beta of a b32 sweep.
 template <int RW>
 __global__ __launch_bounds__(kRsThreads) void k_cheb_step(
     const double *__restrict__ part, int nparts, int n_pad, const DevScalars *sc,
-    const NidState *nid, int j, double *x, double *r, double *d, int phase, int xcd) {
+    const NidState *nid, int j, double *x, double *r, double *d, int phase, int xcd,
+    Beta32Vecs bv) {
     if ((phase == 1 ? nid->mode : nid->k2) <= j) return;
     const int i = rs_block(xcd) * RW + (int)threadIdx.x;
     const double e = part_rowsum_rw<RW>(part, nparts, n_pad, rs_block(xcd) * RW);
@@ -467,7 +512,13 @@ __global__ __launch_bounds__(kRsThreads) void k_cheb_step(
     const double dn = rho1 * rho0 * dv + (2.0 * rho1 / nid->delta) * rv;
     r[i] = rv;
     d[i] = dn;
-    x[i] += dn;
+    const double xn = x[i] + dn;
+    x[i] = xn;
+    if (bv.c) {
+        if (phase == 2) bv.c[i] += dn;
+        const bool last = phase == 2 ? j == nid->k2 - 1 : (nid->k2 == 0 && j == nid->mode - 1);
+        if (last && nid->b32) beta32_xb(bv, sc, i, xn);
+    }
 }
 
 // The mixed plan's restart (k2 > 0): r = b - x - (the residual pass's E x partials) / sig2,
@@ -475,7 +526,8 @@ __global__ __launch_bounds__(kRsThreads) void k_cheb_step(
 template <int RW>
 __global__ __launch_bounds__(kRsThreads) void k_cheb_restart(
     const double *__restrict__ part, int nparts, int n_pad, const DevScalars *sc,
-    const NidState *nid, const double *__restrict__ b, double *x, double *r, double *d, int xcd) {
+    const NidState *nid, const double *__restrict__ b, double *x, double *r, double *d, int xcd,
+    Beta32Vecs bv) {
     if (nid->k2 == 0 || nid->mode == 0) return;
     const int i = rs_block(xcd) * RW + (int)threadIdx.x;
     const double e = part_rowsum_rw<RW>(part, nparts, n_pad, rs_block(xcd) * RW);
@@ -486,6 +538,10 @@ __global__ __launch_bounds__(kRsThreads) void k_cheb_restart(
     r[i] = rv;
     d[i] = dv;
     x[i] = xv + dv;
+    if (bv.c) {
+        bv.c[i] = dv;
+        if (nid->k2 == 1 && nid->b32) beta32_xb(bv, sc, i, xv + dv);
+    }
 }
 
 // out[i] = sum of the nparts partials of row i (setup: power iteration on X X')
@@ -524,11 +580,16 @@ constexpr int kEaThreads = 256;
 // XU: the same pass forming X u (part[wg][row] = sum_c X[row, c] D_c, with D = u), for the
 // right-hand side: no dot products.  T: the element type streamed (double, or float for the
 // mixed plan's fp32 copy of X -- converted exactly to double, so the arithmetic is fp64).
-template <int NR, bool XU, typename T>
+// BANK (k_eapply of kinds 0 and 2; gb may be null: nothing is banked): the chunk's dots X_c' v are kept in gb -- written, or
+// (gacc) added to what is there; thread c < 8 owns column c0 + c, the only writer of gb[c0 + c]
+// in the launch, and reads the old value with the chunk's loads.  (Storing before the update,
+// from LDS sums of its own, cost the fp64 residual pass 3.2 us of 124 at C3.)
+template <int NR, bool XU, typename T, bool BANK = false>
 __device__ __forceinline__ void eapply_body(const T *__restrict__ X, int ldx, int n_pad,
                                             int p_loc, const double *__restrict__ D,
                                             const double *__restrict__ v,
-                                            double *__restrict__ part) {
+                                            double *__restrict__ part, double *gb = nullptr,
+                                            bool gacc = false) {
     __shared__ double ws[4][kEaCols];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     double vr[NR], acc[NR];
@@ -564,6 +625,9 @@ __device__ __forceinline__ void eapply_body(const T *__restrict__ X, int ldx, in
                 }
             }
         }
+        double gold = 0.0;
+        if constexpr (BANK)
+            if (gb && gacc && tid < kEaCols && c0 + tid < p_loc) gold = gb[c0 + tid];
         double xv[kEaCols][NR];
 #pragma unroll
         for (int c = 0; c < kEaCols; ++c)
@@ -591,13 +655,20 @@ __device__ __forceinline__ void eapply_body(const T *__restrict__ X, int ldx, in
 #pragma unroll
             for (int c = 0; c < kEaCols; ++c) ws[wid][c] = s[c];
         __syncthreads();
+        double mine = 0.0;  // BANK: the dot of column c0 + tid, picked from the sums all form
 #pragma unroll
         for (int c = 0; c < kEaCols; ++c) {
             const double dc = (c0 + c < p_loc) ? D[c0 + c] : 0.0;
-            const double f = dc * (((ws[0][c] + ws[1][c]) + ws[2][c]) + ws[3][c]);
+            const double sc = ((ws[0][c] + ws[1][c]) + ws[2][c]) + ws[3][c];
+            if constexpr (BANK)
+                if (c == tid) mine = sc;
+            const double f = dc * sc;
 #pragma unroll
             for (int m = 0; m < NR; ++m) acc[m] = __builtin_fma(xv[c][m], f, acc[m]);
         }
+        // the store follows the chunk's update, off the path to the next chunk's barrier
+        if constexpr (BANK)
+            if (gb && tid < kEaCols && c0 + tid < p_loc) gb[c0 + tid] = gold + mine;
     }
 #pragma unroll
     for (int m = 0; m < NR; ++m) {
@@ -609,6 +680,8 @@ __device__ __forceinline__ void eapply_body(const T *__restrict__ X, int ldx, in
 // KIND (launch_eapply): 0 product j of the first solve (X32 when the mixed plan was taken),
 // 1 X u (XU), 2 the mixed plan's fp64 residual pass, 3 product j of its correction solve.
 // Each launch returns at once unless the device's decision needs it (the gate).
+// gb (an engine that may take the fp32 beta pass, else null): on a b32 sweep the passes over
+// fp64 X bank their dots there -- product 1 and the residual pass write, products j > 1 add.
 template <int NR, int KIND>
 __global__ __launch_bounds__(kEaThreads) void k_eapply(const double *__restrict__ X,
                                                        const float *__restrict__ X32, int ldx,
@@ -616,7 +689,8 @@ __global__ __launch_bounds__(kEaThreads) void k_eapply(const double *__restrict_
                                                        const double *__restrict__ D,
                                                        const double *__restrict__ v,
                                                        const NidState *nid, int j,
-                                                       double *__restrict__ part) {
+                                                       double *__restrict__ part,
+                                                       double *__restrict__ gb) {
     if constexpr (KIND == 1) {
         if (nid->mode == 0) return;
         eapply_body<NR, true, double>(X, ldx, n_pad, p_loc, D, v, part);
@@ -625,10 +699,12 @@ __global__ __launch_bounds__(kEaThreads) void k_eapply(const double *__restrict_
         if (X32 && nid->k2 > 0)
             eapply_body<NR, false, float>(X32, ldx, n_pad, p_loc, D, v, part);
         else
-            eapply_body<NR, false, double>(X, ldx, n_pad, p_loc, D, v, part);
+            eapply_body<NR, false, double, true>(X, ldx, n_pad, p_loc, D, v, part,
+                                                 (gb && nid->b32) ? gb : nullptr, j > 1);
     } else if constexpr (KIND == 2) {
         if (nid->k2 == 0 || nid->mode == 0) return;
-        eapply_body<NR, false, double>(X, ldx, n_pad, p_loc, D, v, part);
+        eapply_body<NR, false, double, true>(X, ldx, n_pad, p_loc, D, v, part,
+                                             (gb && nid->b32) ? gb : nullptr, false);
     } else {
         if (nid->k2 <= j) return;
         eapply_body<NR, false, float>(X32, ldx, n_pad, p_loc, D, v, part);
@@ -758,13 +834,13 @@ void launch_nid_decide_from(hipStream_t s, const double *red, const DevScalars *
 template <int KIND>
 static void launch_pass(hipStream_t s, const double *X, const float *X32, int ldx, int n_pad,
                         int p_loc, const double *D, const double *v, const NidState *nid, int j,
-                        double *part) {
+                        double *part, double *gb = nullptr) {
     const int g = eapply_parts(p_loc, n_pad);
     const int nr = (n_pad + kEaThreads - 1) / kEaThreads;
     auto *kern = nr <= 1 ? k_eapply<1, KIND> : nr <= 2 ? k_eapply<2, KIND>
                : nr <= 4 ? k_eapply<4, KIND> : nr <= 8 ? k_eapply<8, KIND> : k_eapply<16, KIND>;
     if (KIND == 0) note_launch(KF_EAPPLY, (const void *)kern);
-    kern<<<g, kEaThreads, 0, s>>>(X, X32, ldx, n_pad, p_loc, D, v, nid, j, part);
+    kern<<<g, kEaThreads, 0, s>>>(X, X32, ldx, n_pad, p_loc, D, v, nid, j, part, gb);
 }
 
 void launch_nid_xu(hipStream_t s, const double *X, int ldx, const double *u, int ncols,
@@ -775,46 +851,48 @@ void launch_nid_xu(hipStream_t s, const double *X, int ldx, const double *u, int
 void launch_cheb_init(hipStream_t s, const double *xu_part, int nparts, int n, int n_pad,
                       const double *y, const DevScalars *sc, uint64_t k0, uint64_t k1,
                       uint64_t t, const NidState *nid, double *x, double *r, double *d,
-                      double *b) {
+                      double *b, double *xu) {
     if (rowsum_rw(nparts) == 8)
         k_cheb_init<8><<<(n_pad + 7) / 8, kRsThreads, 0, s>>>(xu_part, nparts, n, n_pad, y, sc,
                                                               Key{k0, k1}, t, nid, x, r, d, b,
-                                                              g_rs_xcd);
+                                                              xu, g_rs_xcd);
     else
         k_cheb_init<64><<<(n_pad + 63) / 64, kRsThreads, 0, s>>>(xu_part, nparts, n, n_pad, y,
                                                                  sc, Key{k0, k1}, t, nid, x, r, d,
-                                                                 b, g_rs_xcd);
+                                                                 b, xu, g_rs_xcd);
 }
 
 void launch_cheb_step(hipStream_t s, const double *part, int nparts, int n_pad,
                       const DevScalars *sc, const NidState *nid, int j, double *x, double *r,
-                      double *d, int phase) {
+                      double *d, int phase, const Beta32Vecs *bv) {
+    const Beta32Vecs v = bv ? *bv : Beta32Vecs{};
     if (rowsum_rw(nparts) == 8)
         k_cheb_step<8><<<(n_pad + 7) / 8, kRsThreads, 0, s>>>(part, nparts, n_pad, sc, nid, j, x,
-                                                              r, d, phase, g_rs_xcd);
+                                                              r, d, phase, g_rs_xcd, v);
     else
         k_cheb_step<64><<<(n_pad + 63) / 64, kRsThreads, 0, s>>>(part, nparts, n_pad, sc, nid, j,
-                                                                 x, r, d, phase, g_rs_xcd);
+                                                                 x, r, d, phase, g_rs_xcd, v);
 }
 
 void launch_cheb_restart(hipStream_t s, const double *part, int nparts, int n_pad,
                          const DevScalars *sc, const NidState *nid, const double *b, double *x,
-                         double *r, double *d) {
+                         double *r, double *d, const Beta32Vecs *bv) {
+    const Beta32Vecs v = bv ? *bv : Beta32Vecs{};
     if (rowsum_rw(nparts) == 8)
         k_cheb_restart<8><<<(n_pad + 7) / 8, kRsThreads, 0, s>>>(part, nparts, n_pad, sc, nid, b,
-                                                                 x, r, d, g_rs_xcd);
+                                                                 x, r, d, g_rs_xcd, v);
     else
         k_cheb_restart<64><<<(n_pad + 63) / 64, kRsThreads, 0, s>>>(part, nparts, n_pad, sc, nid,
-                                                                    b, x, r, d, g_rs_xcd);
+                                                                    b, x, r, d, g_rs_xcd, v);
 }
 
 void launch_eapply(hipStream_t s, const double *X, int ldx, int n_pad, int p_loc,
                    const double *D, const double *v, const NidState *nid, int j, double *part,
-                   const float *X32, int kind) {
+                   const float *X32, int kind, double *gb) {
     switch (kind) {
-        case 2: launch_pass<2>(s, X, X32, ldx, n_pad, p_loc, D, v, nid, j, part); break;
+        case 2: launch_pass<2>(s, X, X32, ldx, n_pad, p_loc, D, v, nid, j, part, gb); break;
         case 3: launch_pass<3>(s, X, X32, ldx, n_pad, p_loc, D, v, nid, j, part); break;
-        default: launch_pass<0>(s, X, X32, ldx, n_pad, p_loc, D, v, nid, j, part); break;
+        default: launch_pass<0>(s, X, X32, ldx, n_pad, p_loc, D, v, nid, j, part, gb); break;
     }
 }
 

@@ -558,7 +558,13 @@ void bb_set_trace_budget(long long bytes);
  * compute unit (1), or the 512-thread instance at every size (0, the default).  The narrow
  * instance is about 1.4 x faster in aggregate there and sums rss and S_alpha in another
  * order: its chains match the CPU oracle within the whole-chain tolerances but are not bit
- * for bit those of sequential bridge_reg_stable calls, hence opt-in.
+ * for bit those of sequential bridge_reg_stable calls, hence opt-in;
+ * key 24: beta of a near-identity sweep from the dots X'x the solve's fp64 passes already formed
+ * plus one pass over the fp32 copy of X for the solve's last, small increment (DESIGN.md s6.7;
+ * unsharded dense engines holding that copy, decided on the device per sweep): never (0), where
+ * the increment is certified below 2^-26 of w and the cost model says the halved pass is not
+ * launch-bound (1, the default), or wherever certified (2, for tests at small shapes); beta
+ * agrees with the fp64 pass to rounding, lambda / tau / sig2 of that sweep are the same bits.
  * A negative value changes nothing.  Returns the previous value, or -1 for an unknown key. */
 int bb_set_tuning(int key, int value);
 /* Test hook: the k-th interrupt poll from now reports an interrupt (k >= 0; -1 clears). */
@@ -653,6 +659,10 @@ int bb_kernel_instance(const char *phase, char *buf, int len);
  * holds the fp32 copy of X at all. */
 int bb_engine_nid_mixed(bb_engine *e, unsigned long long *mixed_sweeps,
                         unsigned long long *products32, double *eta, int *k2, int *holds_x32);
+
+/* The fp32 beta pass (bb_set_tuning key 24): sweeps that took it since the
+ * engine was created, and whether the latest sweep did. */
+int bb_engine_nid_beta32(bb_engine *e, unsigned long long *beta32_sweeps, int *b32);
 
 /* Error flags raised on device (rejection-loop caps, non-SPD factorisations). */
 int bb_engine_error_flags(bb_engine *e, uint32_t *flags);

@@ -306,6 +306,14 @@ def set_tuning(key: int, value: int) -> int:
     return int(library().bb_set_tuning(int(key), int(value)))
 
 
+def set_wide_chains(on: bool) -> bool:
+    """Switch the wide fused chains (bb_set_tuning key 25, default off) and return the previous
+    setting.  While on, stable-mixture engines and chain batches created with 32 < P <= 128
+    (P <= N or ortho, alpha known, one device) run whole sweeps in one workgroup, a batch as one
+    launch of a workgroup per chain; what already exists keeps the kernel it was created with."""
+    return bool(library().bb_set_tuning(25, 1 if on else 0))
+
+
 def chol_version() -> int:
     """The device Cholesky chain variant in use (bb_set_chol_version(0) reports it)."""
     return int(library().bb_set_chol_version(0))
@@ -466,7 +474,9 @@ def bridge_reg_stb_chains(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0, sig2_
     """``nchains`` independent chains of bridge.reg.stb in one call, through
     ``.C("bridge_reg_stable_chains", ...)``: chain c is exactly what the c-th of ``nchains``
     consecutive ``bridge_reg_stb`` calls would return.  Small dense designs (P <= 32, P <= N or
-    ortho, alpha known) run every chain side by side in one launch per block of sweeps.
+    ortho, alpha known) run every chain side by side in one launch per block of sweeps; after
+    ``set_wide_chains(True)`` so do designs up to P = 128 (other designs run one chain after
+    another).
 
     Returns a dict: beta (K x M x P), lambda (K x M x P), sig2, tau, alpha (K x M), runtime
     (one number for the batch).
@@ -663,7 +673,8 @@ def bridge_reg_stb_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.
     """``bridge_reg_stb_chains`` returning posterior summaries instead of traces, through
     ``.C("bridge_reg_stable_chains_summary", ...)``: the chains are bit for bit those of the
     trace call under the same key, each ring fill is reduced on the device and nothing but the
-    summaries is copied, so ``nsamp`` and ``nchains`` are not bounded by host memory.
+    summaries is copied, so ``nsamp`` and ``nchains`` are not bounded by host memory.  The batch
+    runs as one launch for P <= 32, and for P <= 128 after ``set_wide_chains(True)``.
 
     Parameters are beta_1..beta_P, sig2, tau, alpha (Q = P + 3, ``names``).  Returns a dict:
     chain_mean, chain_var (K x Q), acov (K x Q x maxlag + 1, biased autocovariances), hmean,
@@ -1415,7 +1426,8 @@ class ChainBatch:
     together by one launch per run (bb_chains_*).  Chain c draws under the key
     (cfg.seed, cfg.stream + c); cfg.trace_capacity is each chain's ring capacity.
     cfg.method = 4 makes it a triangle-mixture batch (omega is the trace's ``lambda``; u and
-    shape through tri_trace / set_tri_state)."""
+    shape through tri_trace / set_tri_state).  A stable-mixture batch needs P <= 32, or
+    P <= 128 when created after ``set_wide_chains(True)`` (it then keeps the wide kernel)."""
 
     def __init__(self, cfg: EngineConfig, nchains: int, X, y):
         L = library()

@@ -125,6 +125,10 @@ int g_nid_b32 = 1;
 // 256-thread instance, two chains per CU (faster in aggregate there; its chains
 // match the oracle but are not bit for bit those of sequential calls)
 int g_chains_packed = 0;
+// bb_set_tuning key 25: stable-mixture engines and chain batches created from now on with
+// 32 < p <= 128 (alpha known, Cholesky or orthogonal draw, one device) run whole sweeps in the
+// fused kernels of bb_wide.hip instead of the general path
+int g_chains_wide = 0;
 static const char *kPhaseNames[PH_COUNT] = {"pre", "scalars", "lambda", "pg", "ozprep", "gram",
                                             "xu", "reduce", "form", "chol", "solve", "beta",
                                             "xb", "alpha", "nid", "eapply", "end"};
@@ -144,6 +148,7 @@ struct bb_engine {
     Method method = AUTO;
     int group = 1;
     bool fused = false;  // small p: whole sweeps in one launch (bb_small.hip)
+    bool wide = false;   // ... by bb_wide.hip's kernel (32 < p <= 128, key 25 set at creation)
     SparseDesign spd;  // method 5: CSC/CSR design and the Gram pair list
     Hyper hy{};
     hipStream_t stream = nullptr;
@@ -856,8 +861,10 @@ struct bb_engine {
             const ChainRun r = chain_run(cfg.stream, t0, count, first_slot, slot_step, cap);
             if (tri())
                 launch_tri_chain(stream, chain_design(), st, tr, r);
-            else
+            else if (!wide)
                 launch_small_chain(stream, chain_design(), st, tr, r);
+            else if (launch_wide_chain(stream, chain_design(), st, tr, r) != 0)
+                throw HipError("no wide fused chain instance for this p");
             if (timing) mark(PH_END);
             xb_stale = true;  // X beta partials refreshed only if a general sweep needs them
             return;
@@ -1467,6 +1474,12 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
     // small p, one device, alpha known: whole sweeps in one single-workgroup launch
     e->fused = (e->method == CHOL || e->ortho()) && c.p <= kSmallChainMaxP && c.world == 1 &&
                e->hy.know_alpha && e->cvec && e->gdiag && (e->ortho() || e->G);
+    // the same for 32 < p <= 128 where key 25 asks for it (bb_wide.hip); the engine keeps the
+    // kernel it was created with
+    e->wide = g_chains_wide && (e->method == CHOL || e->ortho()) && c.p > kSmallChainMaxP &&
+              c.p <= kWideChainMaxP && (c.p <= c.n || e->ortho()) && c.world == 1 &&
+              e->hy.know_alpha && e->cvec && e->gdiag && (e->ortho() || e->G);
+    if (e->wide) e->fused = true;
     if (e->tri())  // bb_tri.hip k_tri_chain (general and orthogonal designs)
         e->fused = c.p <= kTriChainMaxP && c.world == 1 && e->hy.know_alpha &&
                    (!c.ortho || (e->tri_G && e->cvec));
@@ -1643,7 +1656,12 @@ const char *chains_refusal(const bb_config &c) {
     if (c.method != AUTO && c.method != CHOL)
         return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or "
                "1) or the triangle mixture (method 4)";
-    if (c.p > kSmallChainMaxP) return "a chain batch needs p <= 32";
+    if (g_chains_wide) {  // bb_set_tuning key 25: bb_wide.hip's kernel above 32
+        static_assert(kWideChainMaxP == 128, "the message below says 128");
+        if (c.p > kWideChainMaxP) return "a chain batch needs p <= 128 (wide fused chains on)";
+    } else if (c.p > kSmallChainMaxP) {
+        return "a chain batch needs p <= 32";
+    }
     if (c.p > c.n && !c.ortho) return "a chain batch needs p <= n (or the orthogonal design)";
     if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
     return nullptr;
@@ -1727,7 +1745,10 @@ struct bb_chains {
         const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
                              .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
         const ChainRun r = e->chain_run(base_stream, t0, count, first_slot, slot_step, cap);
-        if (!tri())
+        if (wide) {
+            if (launch_wide_chains(e->stream, K, e->chain_design(), st, tr, r) != 0)
+                throw HipError("no wide chain-batch instance for this p");
+        } else if (!tri())
             launch_small_chains(e->stream, K, packed, e->chain_design(), st, tr, r);
         else if (launch_tri_chains(e->stream, K, threads, e->chain_design(), st, tr, r) != 0)
             throw HipError("no triangle chain-batch instance of that many threads");
@@ -1792,6 +1813,9 @@ struct bb_chains {
     int packed = 0;
     // the triangle batch's instance, by its threads per workgroup (bb_chains_create)
     int threads = 512;
+    // bb_wide.hip's k_wide_chains (32 < p <= 128; bb_set_tuning key 25 at creation)
+    bool wide = false;
+    int block() const { return wide ? kWideBlock : 50; }  // sweeps per launch of a .C call
 };
 
 // ---------------------------------------------------------------------------
@@ -2254,7 +2278,8 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
             throw HipError("this design does not run as a fused small chain");
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
-        b->packed = !b->tri() && g_chains_packed && nchains >= 2 * cus;
+        b->wide = b->proto->wide;
+        b->packed = !b->tri() && !b->wide && g_chains_packed && nchains >= 2 * cus;
         // more triangle chains than the 512-thread instance holds at once (one per CU): a
         // narrower instance, several per CU, the same bits
         if (b->tri()) b->threads = tri_chains_threads(c.n, c.p, nchains, cus);
@@ -2292,10 +2317,14 @@ int bb_chains_count(const bb_chains *b) { return b->K; }
 int bb_chains_resident_per_cu(const bb_chains *b) {
     if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
     if (b->tri()) return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads);
+    if (b->wide) return wide_chains_resident_per_cu(b->p);
     return small_chains_resident_per_cu(b->proto->n, b->p, b->packed);
 }
 
-int bb_chains_threads(const bb_chains *b) { return b->tri() ? b->threads : b->packed ? 256 : 512; }
+int bb_chains_threads(const bb_chains *b) {
+    if (b->wide) return wide_chains_threads(b->p);
+    return b->tri() ? b->threads : b->packed ? 256 : 512;
+}
 
 int bb_chains_set_threads(bb_chains *b, int threads) {
     if (!b->tri() || hipSetDevice(b->proto->cfg.device) != hipSuccess ||
@@ -2828,6 +2857,8 @@ struct Chain {
     }
     int init() { return grp ? bb_group_init_state(grp) : bb_engine_init_state(eng[0]); }
     bool fused() const { return !grp && eng.size() == 1 && eng[0]->fused; }
+    // sweeps per launch (and per interrupt poll) of a .C call
+    int block() const { return !fused() ? 10 : eng[0]->wide ? kWideBlock : 50; }
     int run(uint64_t t0, int count, int slot, int step, int mcmc) {
         return grp ? bb_group_run(grp, t0, count, slot, step, mcmc)
                    : bb_engine_run(eng[0], t0, count, slot, step, mcmc);
@@ -2988,7 +3019,9 @@ Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, const T
     // BridgeWrapper.cpp:273-275, 295-297 poll every 10 sweeps.  A fused engine runs a
     // whole block in one launch at ~15-30 us per sweep, so it polls every 50 (< 2 ms) and
     // pays the launch and LDS-staging prologue once per 50 sweeps instead of per 10.
-    const int kBlock = ch.fused() ? 50 : 10;
+    // The wide fused kernel's sweeps are ~100 us: kWideBlock of them keep the poll near the
+    // general path's 10 sweeps in time.
+    const int kBlock = ch.block();
     return drive_schedule(
         ch, kBlock, nburn, t_base, m, b, runtime,
         [&](int slot0, int count, int s0) { return ch.copy_out(slot0, count, s0, out); },
@@ -3075,8 +3108,9 @@ struct ChainsRun {
     void throttle() { b->throttle(); }
 };
 
-// K chains of a small design as one batch on drive_chain's schedule (50-sweep blocks, as a
-// fused single chain).  The trace budget bounds the batch: each chain's ring gets a K-th.
+// K chains of a small design as one batch on drive_chain's schedule (the blocks of a fused
+// single chain: 50 sweeps, kWideBlock on the wide kernel).  The trace budget bounds the batch:
+// each chain's ring gets a K-th.
 // With `sum` the ring fills are not copied out but reduced on the device behind the sweeps
 // (bb_chains::summary_add), and the summaries come back after a complete run.
 Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const double *yp,
@@ -3094,7 +3128,7 @@ Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const doubl
     ChainsRun run{raw, ch->cap};
     if (sum && bb_chains_summary_reset(raw, m, sum->maxlag) != 0) return OUT_ERROR;
     const Outcome o = drive_schedule(
-        run, 50, kd.nburn, kd.t_base, m, b, runtime,
+        run, ch->block(), kd.nburn, kd.t_base, m, b, runtime,
         [&](int slot0, int count, int s0) {
             if (sum)
                 ch->summary_add(slot0, count, s0);
@@ -3180,7 +3214,7 @@ Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const 
         if (o != OUT_OK) o = OUT_ERROR;
         if (o == OUT_OK)
             o = drive_schedule(
-                ch, ch.fused() ? 50 : 10, kd.nburn, kd.t_base, m, b, runtime,
+                ch, ch.block(), kd.nburn, kd.t_base, m, b, runtime,
                 [&](int slot0, int count, int s0) {
                     HIPCHECK(hipSetDevice(e->cfg.device));
                     ts.add(e->stream, ring, slot0, count, s0);
@@ -3396,7 +3430,7 @@ int bb_set_tuning(int key, int value) {
                  {9, &g_shard_proto, 1}, {10, &g_nid_mixed, 1}, {11, &g_nid_poll, 1},
                  {12, &g_rs_xcd, 1},    {13, &g_lam_wave, 1},  {15, &g_lam_lend, 1},
                  {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1},
-                 {24, &g_nid_b32, 2}};
+                 {24, &g_nid_b32, 2},   {25, &g_chains_wide, 1}};
     for (const auto &k : kKeys)
         if (k.key == key) {
             const int old = *k.var;

@@ -475,6 +475,23 @@ void launch_small_chains(hipStream_t s, int nchains, int packed, const ChainDesi
                          const ChainState &c, const ChainTraces &tr, const ChainRun &r);
 int small_chains_resident_per_cu(int n, int p, int packed);
 
+// The same fused stable sweeps for kSmallChainMaxP < p <= kWideChainMaxP (bb_wide.hip; opt-in,
+// bb_set_tuning key 25): X and G are read from memory, U alone is in LDS.  The single chain
+// (k_wide_chain) and the batch (k_wide_chains, a workgroup per chain) run one sweep body, 256
+// threads at p <= 64 and 512 above (wide_chains_threads).  The launchers return -1 if there is
+// no instance for d.p; wide_chains_resident_per_cu: the workgroups the runtime keeps resident
+// on one CU for p coefficients (-1 if the query fails).
+constexpr int kWideChainMaxP = 128;
+int launch_wide_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
+                      const ChainTraces &tr, const ChainRun &r);
+int launch_wide_chains(hipStream_t s, int nchains, const ChainDesign &d, const ChainState &c,
+                       const ChainTraces &tr, const ChainRun &r);
+int wide_chains_resident_per_cu(int p);
+int wide_chains_threads(int p);
+// sweeps per launch of the wide kernels' drivers: one look-ahead of pre-drawn
+// variates
+constexpr int kWideBlock = 16;
+
 // Whole triangle-mixture sweeps (alpha known, p <= kTriChainMaxP) in one single-workgroup
 // launch (bb_tri.hip k_tri_chain): S_alpha / rss, tau and sig2, then omega, u and the
 // rtnorm_gibbs passes of launch_tri_update in one wave.

@@ -277,6 +277,9 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
  * exceed what the device holds at once: later chains start as earlier ones finish.
  * (With bb_set_tuning key 21 set, a batch of at least 2 x compute units chains runs the
  * two-per-CU instance, which is not bit for bit the single engine's chain; see there.)
+ * With bb_set_tuning key 25 set when the batch is created, the bound is p <= 128: designs with
+ * 32 < p <= 128 run bb_wide.hip's k_wide_chains under the same conditions, and chain c is bit
+ * for bit the chain of a bb_engine created under the same setting (it runs k_wide_chain).
  *
  * The triangle mixture (cfg->method == 4; bb_tri.hip k_tri_chains) runs as a batch wherever a
  * single engine runs k_tri_chain fused: p <= 32, p <= n, world == 1, alpha known, either
@@ -564,7 +567,18 @@ void bb_set_trace_budget(long long bytes);
  * unsharded dense engines holding that copy, decided on the device per sweep): never (0), where
  * the increment is certified below 2^-26 of w and the cost model says the halved pass is not
  * launch-bound (1, the default), or wherever certified (2, for tests at small shapes); beta
- * agrees with the fp64 pass to rounding, lambda / tau / sig2 of that sweep are the same bits.
+ * agrees with the fp64 pass to rounding, lambda / tau / sig2 of that sweep are the same bits;
+ * key 25 (wide fused chains): stable-mixture engines and chain batches created from now on
+ * with 32 < p <= 128 -- Cholesky or orthogonal draw, p <= n or ortho, alpha known, world == 1 --
+ * run whole sweeps in one workgroup (bb_wide.hip: k_wide_chain for bb_engine, bridge_reg_stable
+ * and every single-chain call; k_wide_chains, a workgroup per chain, for bb_chains_create and the
+ * *_chains calls, which otherwise refuse p > 32 or run the chains one after another) (1), or
+ * the general path (0, the default).  What exists keeps the kernel it was created with.  The
+ * fused chain uses the general path's counters and matches the CPU oracle within the
+ * whole-chain tolerances; it sums in another order than the general path, so it is not bit for
+ * bit that path's chain, hence opt-in.  Under one setting, chain c of a batch is bit for bit
+ * the c-th of sequential single-chain calls.  (The key is 25, not 22 or 23: tests pin those as
+ * unknown keys.)
  * A negative value changes nothing.  Returns the previous value, or -1 for an unknown key. */
 int bb_set_tuning(int key, int value);
 /* Test hook: the k-th interrupt poll from now reports an interrupt (k >= 0; -1 clears). */

@@ -21,6 +21,14 @@ call of the same build at K = CUs and 4 CUs into profiles/chains_summary_{c1,db}
 call, the trace call, the kernel-only rate, and the share of the summary call's runtime that
 k_trace_summary takes (timed alone on a full ring of a ChainBatch, scaled to the call).
 
+--wide measures the wide fused chains (bb_set_tuning key 25, bb_wide.hip) at the published
+protocol's wider shapes, synthetic designs dbi (442 x 64) and bhi (506 x 103), into
+profiles/chains_wide_{dbi,bhi}.json: alternated within each round, the single call with the key
+off (the general path: K sequential such calls are the baseline a batch has to beat), the
+single call with the key on (k_wide_chain), and batches at K = 8, CUs and 2 CUs with the
+kernel-only rate and the resident workgroups per CU.  Default 1000 samples after a burn-in of
+200 (the traces of 2 CUs chains of 5000 samples would be 4 GB).
+
 Protocol: one warm-up call, then REPS rounds, each round visiting every K (and the
 single-chain bridge_reg_stb call) once, so slow drifts of the device hit every K alike; the
 median over rounds is reported with the min and max beside it.
@@ -30,6 +38,7 @@ median over rounds is reported with the min and max beside it.
                                                           # checkout at DIR (A/B with a parent)
   python tools/bench_chains.py --method tri [--mode single --tree DIR]
   python tools/bench_chains.py --summary [--method tri] [--designs c1]
+  python tools/bench_chains.py --wide [--designs dbi]
 """
 import argparse
 import json
@@ -55,6 +64,15 @@ def designs():
     b = np.r_[3.0, -2.0, 1.5, -1.0, 2.5, np.zeros(5)]
     y = X @ b + 2.0 * rng.standard_normal(442)
     out["db"] = (np.asfortranarray(X), y - y.mean())
+    # the shapes of the protocol's designs with interactions (diabetes 442 x 64, Boston 506 x
+    # 103), synthetic like db: ten / thirteen main effects' worth of signal
+    for name, n, p, seed in (("dbi", 442, 64, 20240502), ("bhi", 506, 103, 20240503)):
+        rng = np.random.default_rng(seed)
+        X = rng.standard_normal((n, p))
+        X -= X.mean(axis=0)
+        b = np.r_[3.0, -2.0, 1.5, -1.0, 2.5, np.zeros(p - 5)]
+        y = X @ b + 2.0 * rng.standard_normal(n)
+        out[name] = (np.asfortranarray(X), y - y.mean())
     return out
 
 
@@ -87,8 +105,8 @@ def spread(v):
     return {"median": float(np.median(v)), "min": float(v[0]), "max": float(v[-1])}
 
 
-def kernel_rate(me, X, y, K, nsamp, threads=0):
-    """Sweeps/s of the batch kernel alone: blocks of 50 sweeps, no traces, one sync.
+def kernel_rate(me, X, y, K, nsamp, threads=0, block=50):
+    """Sweeps/s of the batch kernel alone: blocks of `block` sweeps, no traces, one sync.
     threads: the triangle batch's instance (0: the one the batch selects)."""
     n, p = X.shape
     b = me.bb.ChainBatch(me.config(n, p), K, X, y)
@@ -99,8 +117,8 @@ def kernel_rate(me, X, y, K, nsamp, threads=0):
         b.run(1, 500, 0, 0, 0)
         b.sync()
         t0 = time.perf_counter()
-        for s in range(0, nsamp, 50):
-            b.run(501 + s, 50, -1, 1, 1)
+        for s in range(0, nsamp, block):
+            b.run(501 + s, min(block, nsamp - s), -1, 1, 1)
         b.sync()
         dt = time.perf_counter() - t0
         return K * nsamp / dt, b.resident_per_cu()
@@ -248,11 +266,70 @@ def bench_summary(me, name, X, y, cus, args):
             "kernels": {kname: {"code_sha": _kernel_code.code_sha(kname)}}}
 
 
+WIDE_BLOCK = 16  # sweeps per launch of the wide kernels' drivers (bb_kernels.h kWideBlock)
+
+
+def bench_wide(me, name, X, y, cus, args):
+    """The wide fused chains (key 25) against the general path, alternated within each round.
+    The key is set only around the calls it is measured in and left off."""
+    bb = me.bb
+    Ks = [k for k in dict.fromkeys([8, cus, 2 * cus]) if k <= args.max_chains]
+    nsamp, burn = args.nsamp, args.burn
+
+    def call(on, fn):
+        old = bb.set_tuning(25, 1 if on else 0)
+        try:
+            bb.set_seed(SEED)
+            return fn()
+        finally:
+            bb.set_tuning(25, old)
+
+    for on in (0, 1):  # warm-up
+        call(on, lambda: me.single(y, X, nsamp=100, burn=50))
+    call(1, lambda: me.chains(y, X, nsamp=100, nchains=2, burn=50))
+    off, on_, res = [], [], {}
+    agg = {K: [] for K in Ks}
+    kern = {K: [] for K in Ks}
+    for _ in range(args.reps):
+        off.append(nsamp / call(0, lambda: me.single(y, X, nsamp=nsamp, burn=burn))["runtime"])
+        on_.append(nsamp / call(1, lambda: me.single(y, X, nsamp=nsamp, burn=burn))["runtime"])
+        for K in Ks:
+            out = call(1, lambda: me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn))
+            agg[K].append(K * nsamp / out["runtime"])
+            del out
+            kr, res[K] = call(1, lambda: kernel_rate(me, X, y, K, nsamp, block=WIDE_BLOCK))
+            kern[K].append(kr)
+    s_off, s_on = spread(off), spread(on_)
+    rows = []
+    for K in Ks:
+        a = spread(agg[K])
+        rows.append({"chains": K, "aggregate_sweeps_per_s": a,
+                     "kernel_aggregate_sweeps_per_s": spread(kern[K]),
+                     "resident_per_cu": res[K],
+                     # K sequential key-off calls run at the single call's rate in aggregate
+                     "vs_sequential_general_path": a["median"] / s_off["median"],
+                     "beats_sequential_beyond_spread": a["min"] > s_off["max"]})
+    from bayesbridge_amd import _kernel_code
+
+    inst = "64, 256" if X.shape[1] <= 64 else "128, 512"
+    kernels = {k: {"code_sha": _kernel_code.code_sha(k)}
+               for k in (f"bb::k_wide_chain<{inst}>", f"bb::k_wide_chains<{inst}>")}
+    return {"design": name, "n": int(X.shape[0]), "p": int(X.shape[1]), "nsamp": nsamp,
+            "burn": burn, "reps": args.reps, "compute_units": cus,
+            "single_call_general_path_sweeps_per_s": s_off,
+            "single_call_wide_sweeps_per_s": s_on,
+            "single_wide_vs_general_path": s_on["median"] / s_off["median"],
+            "single_wide_beats_general_path_beyond_spread": s_on["min"] > s_off["max"],
+            "chains": rows, "kernels": kernels}
+
+
 def bench_single(me, args):
     """The single-chain call alone at both designs (one JSON line): the A/B against another
     checkout."""
     out = {}
     for name, (X, y) in designs().items():
+        if name not in args.designs.split(","):
+            continue
         me.bb.set_seed(SEED)
         me.single(y, X, nsamp=200, burn=100)
         v = []
@@ -269,9 +346,9 @@ def main():
     ap.add_argument("--mode", choices=["chains", "single"], default="chains")
     ap.add_argument("--method", choices=["stable", "tri"], default="stable")
     ap.add_argument("--tree", default=ROOT, help="checkout whose bayesbridge_amd is measured")
-    ap.add_argument("--designs", default="c1,db")
-    ap.add_argument("--nsamp", type=int, default=5000)
-    ap.add_argument("--burn", type=int, default=500)
+    ap.add_argument("--designs", default=None, help="default c1,db (--wide: dbi,bhi)")
+    ap.add_argument("--nsamp", type=int, default=None, help="default 5000 (--wide: 1000)")
+    ap.add_argument("--burn", type=int, default=None, help="default 500 (--wide: 200)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--max-chains", type=int, default=1 << 20)
     ap.add_argument("--tuning", default="",
@@ -280,11 +357,16 @@ def main():
                     default=[512, 256, 128], help="triangle batch instances to compare (threads)")
     ap.add_argument("--summary", action="store_true",
                     help="the summary mode against the trace call (profiles/chains_summary_*)")
+    ap.add_argument("--wide", action="store_true",
+                    help="the wide fused chains (key 25) at dbi / bhi (profiles/chains_wide_*)")
     ap.add_argument("--chains", type=lambda v: [int(t) for t in v.split(",")], default=None,
                     help="--summary: the batch sizes (default CUs,4 CUs)")
     ap.add_argument("--tag", default="", help="suffix of the output files' names")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
+    args.designs = args.designs or ("dbi,bhi" if args.wide else "c1,db")
+    args.nsamp = args.nsamp or (1000 if args.wide else 5000)
+    args.burn = args.burn if args.burn is not None else (200 if args.wide else 500)
     sys.path.insert(0, os.path.abspath(args.tree))
     import torch
 
@@ -301,6 +383,23 @@ def main():
            else int(torch.cuda.get_device_properties(0).multi_processor_count))
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
+            continue
+        if args.wide:
+            rec = bench_wide(me, name, X, y, cus, args)
+            rec["source_sha"] = bb._build.source_sha()
+            with open(os.path.join(args.out_dir, f"chains_wide_{name}{args.tag}.json"), "w") as f:
+                json.dump(rec, f, indent=1)
+                f.write("\n")
+            g, w = rec["single_call_general_path_sweeps_per_s"], rec["single_call_wide_sweeps_per_s"]
+            print(f"{name} single call: general path {g['median']:.0f} sweeps/s [{g['min']:.0f}, "
+                  f"{g['max']:.0f}]  wide {w['median']:.0f} [{w['min']:.0f}, {w['max']:.0f}]  "
+                  f"x{rec['single_wide_vs_general_path']:.2f}", flush=True)
+            for r in rec["chains"]:
+                a, k = r["aggregate_sweeps_per_s"], r["kernel_aggregate_sweeps_per_s"]
+                print(f"{name} K={r['chains']:5d} aggregate {a['median']:.0f} sweeps/s "
+                      f"[{a['min']:.0f}, {a['max']:.0f}]  kernel {k['median']:.0f}  "
+                      f"x{r['vs_sequential_general_path']:.1f} sequential  resident/CU "
+                      f"{r['resident_per_cu']}", flush=True)
             continue
         if args.summary:
             rec = bench_summary(me, name, X, y, cus, args)

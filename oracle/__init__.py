@@ -4,10 +4,16 @@ Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline``
 leg import this package, and only as the checker.  The product
 (``bayesbridge_amd`` / ``BayesBridge.so``) never imports, links or calls it.
 
-PARITY UNPINNED against reference outputs (no reference fixtures exist and the
-reference cannot be built or run here -- see ``bb_oracle.c`` header and
-DESIGN.md); pinned instead by Philox KATs, numpy's Philox, analytic moments of
-the tilted stable law and exact-posterior quadrature (tests/test_oracle_cpu.py).
+The tilted-stable sampler (``retstable``) and lambda | beta, tau (``sample_lambda``) are
+PINNED to the reference's own compiled ``retstable_LD`` on shared variates: ``oracle/ref.py``
+builds the reference's unmodified ``Code/C/retstable.cpp`` against a stand-in ``RNG.hpp``
+(``ref_shim/``: a tape player serving unif / norm / expon_rate, restating nothing), replays
+the oracle's tape (``retstable_tape``) through it, and tests/golden/ref_retstable.npz keeps
+what it returned (tests/test_ref_pin_cpu.py, bit for bit).  Everything behind
+the reference's ``Matrix.h`` (tau, sig2, alpha, the beta maps, the triangle sampler, EM) is
+PARITY UNPINNED against reference outputs -- that header needs a whole matrix library -- and
+pinned instead by Philox KATs, numpy's Philox, analytic moments of the tilted stable law
+and exact-posterior quadrature (tests/test_oracle_cpu.py).
 """
 from __future__ import annotations
 
@@ -59,6 +65,11 @@ def lib():
         L.bbo_retstable.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, _u64p,
                                     ctypes.c_uint64, ctypes.c_uint64, _lp, _lp]
         L.bbo_retstable.restype = ctypes.c_double
+        L.bbo_retstable_tape.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, _u64p,
+                                         ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.POINTER(ctypes.c_int), _dp, ctypes.c_long, _lp,
+                                         ctypes.c_long, _lp, _lp, _lp]
+        L.bbo_retstable_tape.restype = ctypes.c_double
         L.bbo_retstable_batch.argtypes = [_dp, _dp, _dp, _dp, ctypes.c_long, _u64p,
                                           ctypes.c_uint64]
         L.bbo_sample_lambda.argtypes = [_dp, _dp, ctypes.c_long, ctypes.c_double,
@@ -134,6 +145,29 @@ def retstable(h, alpha, V0=1.0, seed=0, stream=0, t=0, j=0, counts=False):
     return x
 
 
+TAPE_UNIF, TAPE_NORM, TAPE_EXPON, TAPE_ANY = 0, 1, 2, 3
+
+
+def retstable_tape(h, alpha, V0=1.0, seed=0, stream=0, t=0, j=0, cap=4096):
+    """``retstable`` with its tape: the variates of the draw in the order the reference's
+    ``retstable_LD`` asks its RNG for them.  Returns dict(x, kind (TAPE_*), value,
+    inner (inner attempts of each outer attempt), n_outer, n_inner)."""
+    L = lib()
+    while True:
+        kind = np.zeros(cap, dtype=np.intc)
+        value = np.zeros(cap)
+        inner = np.zeros(cap, dtype=np.int_)
+        n, no, ni = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        x = L.bbo_retstable_tape(float(h), float(alpha), float(V0), _key(seed, stream), t, j,
+                                 kind.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _ptr(value),
+                                 cap, inner.ctypes.data_as(_lp), cap, ctypes.byref(n),
+                                 ctypes.byref(no), ctypes.byref(ni))
+        if n.value <= cap and no.value <= cap:
+            return dict(x=x, kind=kind[:n.value].copy(), value=value[:n.value].copy(),
+                        inner=inner[:no.value].copy(), n_outer=no.value, n_inner=ni.value)
+        cap = max(n.value, no.value)
+
+
 def retstable_batch(alpha, V0, h, seed=0, stream=0, t=0):
     """Mirror of ``.C("retstable_LD", x, alpha, V0, h, num)`` (BridgeWrapper.cpp:965-984)."""
     alpha = np.ascontiguousarray(alpha, dtype=np.float64)
@@ -143,6 +177,25 @@ def retstable_batch(alpha, V0, h, seed=0, stream=0, t=0):
     lib().bbo_retstable_batch(_ptr(x), _ptr(alpha), _ptr(V0), _ptr(h), h.shape[0],
                               _key(seed, stream), t)
     return x
+
+
+def retstable_counts(alpha, V0, h, seed=0, stream=0, t=0, j0=0):
+    """``retstable_batch`` draw by draw, with the attempts of each: (x, n_outer, n_inner)."""
+    num = len(h)
+    x, no, ni = np.zeros(num), np.zeros(num, dtype=np.int64), np.zeros(num, dtype=np.int64)
+    for i in range(num):
+        x[i], no[i], ni[i] = retstable(h[i], alpha[i], V0[i], seed, stream, t, j0 + i,
+                                       counts=True)
+    return x, no, ni
+
+
+def lambda_counts(beta, alpha, tau, seed, stream, t, j0=0):
+    """The attempts (n_outer, n_inner) of each draw of ``sample_lambda``."""
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    h = beta * beta / (tau * tau)
+    _, no, ni = retstable_counts(np.full(h.shape[0], 0.5 * alpha), np.ones(h.shape[0]), h, seed,
+                                 stream, t, j0)
+    return no, ni
 
 
 def sample_lambda(beta, alpha, tau, seed, stream, t, j0=0):

@@ -6,11 +6,16 @@
  * bench.py's cpu_baseline leg.  Nothing in the product (bayesbridge_amd/,
  * BayesBridge.so) links, loads or calls this file.
  *
- * PARITY UNPINNED against the reference's own outputs: the reference ships no
- * golden vectors / fixtures for this path, R is not installed,
- * and the reference C++ cannot be built here (Code/C/retstable.h:7 includes the
- * un-vendored RNG.hpp; BridgeRegression.h:67-68 includes the un-vendored
- * Matrix.h / RNG.hpp).  This restatement is pinned instead by
+ * The tilted-stable sampler (bbo_retstable) and lambda | beta, tau (bbo_sample_lambda)
+ * are PINNED to the reference's own compiled retstable_LD: `make ref` builds the
+ * reference's unmodified Code/C/retstable.cpp against a stand-in RNG.hpp (ref_shim/: a
+ * tape player for the three variate calls the file uses), ref_driver.cpp replays the
+ * tape of bbo_retstable_tape through it, and tests/test_ref_pin_cpu.py requires bit
+ * equality with what it returned (tests/golden/ref_retstable.npz).
+ *
+ * The rest is PARITY UNPINNED against the reference's own outputs: it ships no golden
+ * vectors / fixtures, R is not installed, and BridgeRegression.h:67-68
+ * includes the un-vendored Matrix.h (a whole matrix library) / RNG.hpp.  It is pinned by
  *   - Philox4x64-10 known-answer vectors (Random123 KAT) and numpy's
  *     independent Philox implementation (tests/test_oracle_cpu.py),
  *   - analytic properties of the exponentially tilted stable law
@@ -150,9 +155,34 @@ static double BdB0(double x, double alpha) /* retstable.cpp:73-77 */
  * r0=V, r1=W, r2=W_ (or Box-Muller u1), r3=Box-Muller u2; outer r0=V_,
  * r1=unif / exp / Box-Muller u1, r2=Box-Muller u2.
  * *n_outer / *n_inner (may be NULL) return the attempts consumed.
+ *
+ * tp (may be NULL) records the tape of the draw: every variate in the order the
+ * reference's retstable_LD asks its RNG for it, with the kind of call that asks
+ * (oracle/ref.py replays it through the reference's compiled sampler).
  */
-double bbo_retstable(double h, double alpha, double V0, const uint64_t key[2],
-                     uint64_t t, uint64_t j, long *n_outer, long *n_inner)
+enum { BBO_TAPE_UNIF = 0, BBO_TAPE_NORM = 1, BBO_TAPE_EXPON = 2 };
+
+struct bbo_tape {
+    int *kind;      /* BBO_TAPE_* of item k */
+    double *value;  /* the variate served */
+    long *inner;    /* inner attempts of outer attempt o */
+    long cap, cap_outer;
+    long n; /* items needed (recorded: min(n, cap)) */
+};
+
+static inline void tape_put(struct bbo_tape *tp, int kind, double value)
+{
+    if (!tp) return;
+    if (tp->n < tp->cap) {
+        tp->kind[tp->n] = kind;
+        tp->value[tp->n] = value;
+    }
+    ++tp->n;
+}
+
+static double retstable_core(double h, double alpha, double V0, const uint64_t key[2],
+                             uint64_t t, uint64_t j, long *n_outer, long *n_inner,
+                             struct bbo_tape *tp)
 {
     if (n_outer) *n_outer = 0;
     if (n_inner) *n_inner = 0;
@@ -184,18 +214,25 @@ double bbo_retstable(double h, double alpha, double V0, const uint64_t key[2],
             draw4(key, t, BBO_KIND_LAMBDA_INNER, j, o, i, r);
             ++ninner;
             double V = r[0];
+            tape_put(tp, BBO_TAPE_UNIF, V);
             if (gamma >= 1) {
-                if (V < w1 / (w1 + w2)) U = fabs(bm_normal(r[2], r[3])) / sgamma;
-                else {
+                if (V < w1 / (w1 + w2)) {
+                    double Nn = bm_normal(r[2], r[3]);
+                    tape_put(tp, BBO_TAPE_NORM, Nn);
+                    U = fabs(Nn) / sgamma;
+                } else {
                     double W_ = r[2];
+                    tape_put(tp, BBO_TAPE_UNIF, W_);
                     U = M_PI * (1. - W_ * W_);
                 }
             } else {
                 double W_ = r[2];
+                tape_put(tp, BBO_TAPE_UNIF, W_);
                 if (V < w3 / (w2 + w3)) U = M_PI * W_;
                 else U = M_PI * (1. - W_ * W_);
             }
             double W = r[1];
+            tape_put(tp, BBO_TAPE_UNIF, W);
             double zeta = sqrt(BdB0(U, alpha));
             z = 1 / (1 - pow(1 + alpha * zeta / sgamma, -1 / alpha));
             double rho = M_PI * exp(-lambda_alpha * (1. - 1. / (zeta * zeta))) /
@@ -206,7 +243,10 @@ double bbo_retstable(double h, double alpha, double V0, const uint64_t key[2],
             if (U >= 0 && U <= M_PI && gamma < 1) d += xi;
             rho *= d;
             Z = W * rho;
-            if (U < M_PI && Z <= 1.) break;
+            if (U < M_PI && Z <= 1.) {
+                if (tp && (long)o < tp->cap_outer) tp->inner[o] = (long)i + 1;
+                break;
+            }
         }
         double a = pow(A_(U, alpha), 1. / (1. - alpha)); /* :212-218 */
         double m = pow(b / a, alpha) * lambda_alpha;
@@ -219,13 +259,18 @@ double bbo_retstable(double h, double alpha, double V0, const uint64_t key[2],
         double r[4];
         draw4(key, t, BBO_KIND_LAMBDA_OUTER, j, o, 0, r);
         double V_ = r[0], N_ = 0., E_ = 0.; /* :224-238 */
+        tape_put(tp, BBO_TAPE_UNIF, V_);
         if (V_ < a1 / s) {
             N_ = bm_normal(r[1], r[2]);
+            tape_put(tp, BBO_TAPE_NORM, N_);
             X = m - delta * fabs(N_);
         } else {
-            if (V_ < (a1 + a2) / s) X = m + delta * r[1];
-            else {
+            if (V_ < (a1 + a2) / s) {
+                tape_put(tp, BBO_TAPE_UNIF, r[1]);
+                X = m + delta * r[1];
+            } else {
                 E_ = -log(r[1]);
+                tape_put(tp, BBO_TAPE_EXPON, E_);
                 X = m + delta + E_ * a3;
             }
         }
@@ -241,6 +286,26 @@ double bbo_retstable(double h, double alpha, double V0, const uint64_t key[2],
         }
     }
     return exp(1 / alpha * log(V0) - b * log(X)); /* :270 */
+}
+
+double bbo_retstable(double h, double alpha, double V0, const uint64_t key[2],
+                     uint64_t t, uint64_t j, long *n_outer, long *n_inner)
+{
+    return retstable_core(h, alpha, V0, key, t, j, n_outer, n_inner, NULL);
+}
+
+/* bbo_retstable with its tape: kind[k] / value[k] for k < min(*n_items, cap), and the
+ * inner attempts of each outer attempt in inner_per_outer[o], o < min(*n_outer, cap_outer).
+ * *n_items is the length the draw needs; a tape cut at cap is short, never wrong. */
+double bbo_retstable_tape(double h, double alpha, double V0, const uint64_t key[2],
+                          uint64_t t, uint64_t j, int *kind, double *value, long cap,
+                          long *inner_per_outer, long cap_outer, long *n_items,
+                          long *n_outer, long *n_inner)
+{
+    struct bbo_tape tp = {kind, value, inner_per_outer, cap, cap_outer, 0};
+    double x = retstable_core(h, alpha, V0, key, t, j, n_outer, n_inner, &tp);
+    if (n_items) *n_items = tp.n;
+    return x;
 }
 
 /* BridgeWrapper.cpp:965-984 (batch .C entry), counters (t, j = i). */

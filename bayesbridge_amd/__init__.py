@@ -314,6 +314,16 @@ def set_wide_chains(on: bool) -> bool:
     return bool(library().bb_set_tuning(25, 1 if on else 0))
 
 
+def set_fused_alpha(on: bool) -> bool:
+    """Switch alpha sampling inside the fused small chains (bb_set_tuning key 26, default off)
+    and return the previous setting.  While on, stable-mixture engines and chain batches created
+    with P <= 32 and alpha unknown (``alpha <= 0``; P <= N or ortho, one device) run whole
+    sweeps, the alpha Metropolis-Hastings step included, in one workgroup, a batch as one launch
+    of a 512-thread workgroup per chain; what already exists keeps the path it was created
+    with."""
+    return bool(library().bb_set_tuning(26, 1 if on else 0))
+
+
 def chol_version() -> int:
     """The device Cholesky chain variant in use (bb_set_chol_version(0) reports it)."""
     return int(library().bb_set_chol_version(0))
@@ -475,8 +485,9 @@ def bridge_reg_stb_chains(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0, sig2_
     ``.C("bridge_reg_stable_chains", ...)``: chain c is exactly what the c-th of ``nchains``
     consecutive ``bridge_reg_stb`` calls would return.  Small dense designs (P <= 32, P <= N or
     ortho, alpha known) run every chain side by side in one launch per block of sweeps; after
-    ``set_wide_chains(True)`` so do designs up to P = 128 (other designs run one chain after
-    another).
+    ``set_wide_chains(True)`` so do designs up to P = 128, and after ``set_fused_alpha(True)``
+    so do designs with P <= 32 and alpha unknown (``alpha <= 0``), whose alpha is then sampled
+    inside the launch (other designs run one chain after another).
 
     Returns a dict: beta (K x M x P), lambda (K x M x P), sig2, tau, alpha (K x M), runtime
     (one number for the batch).
@@ -674,7 +685,9 @@ def bridge_reg_stb_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.
     ``.C("bridge_reg_stable_chains_summary", ...)``: the chains are bit for bit those of the
     trace call under the same key, each ring fill is reduced on the device and nothing but the
     summaries is copied, so ``nsamp`` and ``nchains`` are not bounded by host memory.  The batch
-    runs as one launch for P <= 32, and for P <= 128 after ``set_wide_chains(True)``.
+    runs as one launch for P <= 32, and for P <= 128 after ``set_wide_chains(True)``; with alpha
+    unknown (``alpha <= 0``) it does so for P <= 32 after ``set_fused_alpha(True)``, and the
+    alpha column then carries that chain's draws.
 
     Parameters are beta_1..beta_P, sig2, tau, alpha (Q = P + 3, ``names``).  Returns a dict:
     chain_mean, chain_var (K x Q), acov (K x Q x maxlag + 1, biased autocovariances), hmean,
@@ -1427,7 +1440,9 @@ class ChainBatch:
     (cfg.seed, cfg.stream + c); cfg.trace_capacity is each chain's ring capacity.
     cfg.method = 4 makes it a triangle-mixture batch (omega is the trace's ``lambda``; u and
     shape through tri_trace / set_tri_state).  A stable-mixture batch needs P <= 32, or
-    P <= 128 when created after ``set_wide_chains(True)`` (it then keeps the wide kernel)."""
+    P <= 128 when created after ``set_wide_chains(True)`` (it then keeps the wide kernel); with
+    cfg.true_alpha <= 0 it needs P <= 32 and ``set_fused_alpha(True)`` at creation, and each
+    chain then samples its alpha inside the launch (``run``'s mcmc_phase selects the prior)."""
 
     def __init__(self, cfg: EngineConfig, nchains: int, X, y):
         L = library()

@@ -129,6 +129,11 @@ int g_chains_packed = 0;
 // 32 < p <= 128 (alpha known, Cholesky or orthogonal draw, one device) run whole sweeps in the
 // fused kernels of bb_wide.hip instead of the general path
 int g_chains_wide = 0;
+// bb_set_tuning key 26: stable-mixture engines and chain batches created from now on with
+// p <= 32 and alpha unknown (Cholesky or orthogonal draw, one device) run the fused sweeps of
+// bb_small.hip with the alpha MH step inside (bb_small_mh.hip's instances, 512 threads) instead
+// of the general path
+int g_fused_alpha = 0;
 static const char *kPhaseNames[PH_COUNT] = {"pre", "scalars", "lambda", "pg", "ozprep", "gram",
                                             "xu", "reduce", "form", "chol", "solve", "beta",
                                             "xb", "alpha", "nid", "eapply", "end"};
@@ -843,9 +848,10 @@ struct bb_engine {
                 .ortho = tri() ? cfg.ortho : ortho(), .betaburn = cfg.betaburn, .hy = hy};
     }
     ChainRun chain_run(uint64_t k1, uint64_t t0, int count, int first_slot, int slot_step,
-                       int ring_cap) const {
+                       int ring_cap, int mcmc_phase) const {
         return {.k0 = cfg.seed, .k1 = k1, .t0 = t0, .count = count, .first_slot = first_slot,
-                .slot_step = slot_step, .cap = ring_cap};
+                .slot_step = slot_step, .cap = ring_cap, .pr_a = alpha_prior_a(mcmc_phase),
+                .pr_b = hy.alpha_b};
     }
 
     // `count` sweeps from t0 into slots first_slot + k slot_step (mod cap)
@@ -858,7 +864,8 @@ struct bb_engine {
             const ChainState st{.beta = beta, .lam = lam, .u = u, .shape = D, .sc = sc, .err = err};
             const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
                                  .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
-            const ChainRun r = chain_run(cfg.stream, t0, count, first_slot, slot_step, cap);
+            const ChainRun r =
+                chain_run(cfg.stream, t0, count, first_slot, slot_step, cap, mcmc_phase);
             if (tri())
                 launch_tri_chain(stream, chain_design(), st, tr, r);
             else if (!wide)
@@ -1471,9 +1478,11 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
         }
     }
     if (e->tri()) tri_setup(e, Xh);
-    // small p, one device, alpha known: whole sweeps in one single-workgroup launch
+    // small p, one device, alpha known (or, where key 26 asks for it, sampled in the kernel):
+    // whole sweeps in one single-workgroup launch; the engine keeps the path it was created with
     e->fused = (e->method == CHOL || e->ortho()) && c.p <= kSmallChainMaxP && c.world == 1 &&
-               e->hy.know_alpha && e->cvec && e->gdiag && (e->ortho() || e->G);
+               (e->hy.know_alpha || g_fused_alpha) && e->cvec && e->gdiag &&
+               (e->ortho() || e->G);
     // the same for 32 < p <= 128 where key 25 asks for it (bb_wide.hip); the engine keeps the
     // kernel it was created with
     e->wide = g_chains_wide && (e->method == CHOL || e->ortho()) && c.p > kSmallChainMaxP &&
@@ -1663,7 +1672,9 @@ const char *chains_refusal(const bb_config &c) {
         return "a chain batch needs p <= 32";
     }
     if (c.p > c.n && !c.ortho) return "a chain batch needs p <= n (or the orthogonal design)";
-    if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
+    // bb_set_tuning key 26: bb_small_mh.hip's instances sample alpha, at p <= 32 alone
+    if (!(c.true_alpha > 0) && !(g_fused_alpha && c.p <= kSmallChainMaxP))
+        return "a chain batch needs alpha known (true_alpha > 0)";
     return nullptr;
 }
 
@@ -1739,12 +1750,13 @@ struct bb_chains {
         HIPCHECK(hipStreamSynchronize(s));
     }
 
-    void run(uint64_t t0, int count, int first_slot, int slot_step) {
+    void run(uint64_t t0, int count, int first_slot, int slot_step, int mcmc_phase) {
         bb_engine *e = proto;
         const ChainState st{.beta = beta, .lam = lam, .u = u, .shape = shape, .sc = sc, .err = err};
         const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
                              .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
-        const ChainRun r = e->chain_run(base_stream, t0, count, first_slot, slot_step, cap);
+        const ChainRun r =
+            e->chain_run(base_stream, t0, count, first_slot, slot_step, cap, mcmc_phase);
         if (wide) {
             if (launch_wide_chains(e->stream, K, e->chain_design(), st, tr, r) != 0)
                 throw HipError("no wide chain-batch instance for this p");
@@ -2279,7 +2291,9 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
         b->wide = b->proto->wide;
-        b->packed = !b->tri() && !b->wide && g_chains_packed && nchains >= 2 * cus;
+        // (alpha sampled, key 26: the 512-thread instance at every K, there is no packed one)
+        b->packed = !b->tri() && !b->wide && g_chains_packed && nchains >= 2 * cus &&
+                    b->proto->hy.know_alpha;
         // more triangle chains than the 512-thread instance holds at once (one per CU): a
         // narrower instance, several per CU, the same bits
         if (b->tri()) b->threads = tri_chains_threads(c.n, c.p, nchains, cus);
@@ -2318,7 +2332,7 @@ int bb_chains_resident_per_cu(const bb_chains *b) {
     if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
     if (b->tri()) return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads);
     if (b->wide) return wide_chains_resident_per_cu(b->p);
-    return small_chains_resident_per_cu(b->proto->n, b->p, b->packed);
+    return small_chains_resident_per_cu(b->proto->n, b->p, b->packed, !b->proto->hy.know_alpha);
 }
 
 int bb_chains_threads(const bb_chains *b) {
@@ -2342,9 +2356,9 @@ int bb_chains_init_state(bb_chains *b) {
 
 int bb_chains_run(bb_chains *b, uint64_t t0, int count, int first_slot, int slot_step,
                   int mcmc_phase) {
-    (void)mcmc_phase;  // selects the prior of the alpha MH step: alpha is known here
+    // mcmc_phase selects the prior of the alpha MH step (batches created under key 26)
     return guarded(b->proto->cfg.device, [&] {
-        b->run(t0, count, first_slot, slot_step);
+        b->run(t0, count, first_slot, slot_step, mcmc_phase);
         HIPCHECK(hipGetLastError());
     });
 }
@@ -3430,7 +3444,7 @@ int bb_set_tuning(int key, int value) {
                  {9, &g_shard_proto, 1}, {10, &g_nid_mixed, 1}, {11, &g_nid_poll, 1},
                  {12, &g_rs_xcd, 1},    {13, &g_lam_wave, 1},  {15, &g_lam_lend, 1},
                  {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1},
-                 {24, &g_nid_b32, 2},   {25, &g_chains_wide, 1}};
+                 {24, &g_nid_b32, 2},   {25, &g_chains_wide, 1}, {26, &g_fused_alpha, 1}};
     for (const auto &k : kKeys)
         if (k.key == key) {
             const int old = *k.var;

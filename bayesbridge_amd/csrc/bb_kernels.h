@@ -455,14 +455,19 @@ struct ChainTraces {
 };
 // `count` sweeps under the key (k0, k1) (chain c of a batch: (k0, k1 + c)): sweep k uses counter
 // t0 + k and trace slot (first_slot + k slot_step) % cap (first_slot < 0: none).
+// (pr_a, pr_b): the Beta prior of the small chain's alpha MH step in this launch's phase (the
+// engine's alpha_prior_a; unused where alpha is known).
 struct ChainRun {
     uint64_t k0, k1, t0;
     int count, first_slot, slot_step, cap;
+    double pr_a = 0.0, pr_b = 0.0;
 };
 
 // Small-p fused chain (bb_small.hip): whole sweeps (tau, sig2, lambda, beta by the p x p
 // Cholesky draw, or the orthogonal-design draw) in ONE single-workgroup launch, for
-// p <= kSmallChainMaxP and alpha known.
+// p <= kSmallChainMaxP; with alpha known, or (d.hy.know_alpha == 0: engines and batches created
+// under bb_set_tuning key 26) sampled by the MH step of launch_alpha_mh after beta, under the
+// prior (r.pr_a, r.pr_b) -- bb_small_mh.hip's k_small_chain_mh / k_small_chains_mh, 512 threads.
 constexpr int kSmallChainMaxP = 32;
 void launch_small_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
                         const ChainTraces &tr, const ChainRun &r);
@@ -470,10 +475,11 @@ void launch_small_chain(hipStream_t s, const ChainDesign &d, const ChainState &c
 // The same sweeps for `nchains` independent chains in one launch, a workgroup per chain
 // (k_small_chains).  small_chains_resident_per_cu: the workgroups the runtime keeps resident on
 // one CU for an n x p design (-1 if the query fails).  packed: the 256-thread instance, two
-// workgroups per CU (another summation order of rss and S_alpha than the 512-thread one).
+// workgroups per CU (another summation order of rss and S_alpha than the 512-thread one); it is
+// ignored where alpha is sampled, which has the 512-thread instance alone (mh: that instance).
 void launch_small_chains(hipStream_t s, int nchains, int packed, const ChainDesign &d,
                          const ChainState &c, const ChainTraces &tr, const ChainRun &r);
-int small_chains_resident_per_cu(int n, int p, int packed);
+int small_chains_resident_per_cu(int n, int p, int packed, int mh);
 
 // The same fused stable sweeps for kSmallChainMaxP < p <= kWideChainMaxP (bb_wide.hip; opt-in,
 // bb_set_tuning key 25): X and G are read from memory, U alone is in LDS.  The single chain

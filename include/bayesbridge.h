@@ -280,6 +280,10 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
  * With bb_set_tuning key 25 set when the batch is created, the bound is p <= 128: designs with
  * 32 < p <= 128 run bb_wide.hip's k_wide_chains under the same conditions, and chain c is bit
  * for bit the chain of a bb_engine created under the same setting (it runs k_wide_chain).
+ * With bb_set_tuning key 26 set when the batch is created, a stable-mixture batch with p <= 32
+ * may have alpha unknown (true_alpha <= 0): each chain samples its alpha inside the launch
+ * (k_small_chains_mh, 512 threads), under the prior pair that bb_chains_run's mcmc_phase selects
+ * as bb_engine_run's does, and is bit for bit the chain of a bb_engine created under the key.
  *
  * The triangle mixture (cfg->method == 4; bb_tri.hip k_tri_chains) runs as a batch wherever a
  * single engine runs k_tri_chain fused: p <= 32, p <= n, world == 1, alpha known, either
@@ -579,6 +583,19 @@ void bb_set_trace_budget(long long bytes);
  * bit that path's chain, hence opt-in.  Under one setting, chain c of a batch is bit for bit
  * the c-th of sequential single-chain calls.  (The key is 25, not 22 or 23: tests pin those as
  * unknown keys.)
+ * key 26 (alpha sampled in the fused small chains): stable-mixture engines and chain batches
+ * created from now on with p <= 32 and alpha unknown (true_alpha <= 0) -- Cholesky or orthogonal
+ * draw, p <= n or ortho, world == 1 -- run whole sweeps, the alpha Metropolis-Hastings step
+ * included, in one workgroup (bb_small_mh.hip: k_small_chain_mh for bb_engine, bridge_reg_stable
+ * and every single-chain call; k_small_chains_mh, a 512-thread workgroup per chain at every
+ * batch size, key 21 or not, for bb_chains_create and the *_chains calls, which otherwise refuse
+ * alpha unknown or run the chains one after another) (1), or the general path (0, the default).
+ * What exists keeps the path it was created with.  The fused chain uses the general path's
+ * counters and the reference's prior pair of each phase, and matches the CPU oracle within the
+ * whole-chain tolerances; it sums in another order than the general path, hence opt-in.  Under
+ * one setting, chain c of a batch is bit for bit the c-th of sequential single-chain calls.
+ * The triangle mixture, 32 < p <= 128 (key 25 or not), sharded, sparse and logistic engines are
+ * as they are without the key.
  * A negative value changes nothing.  Returns the previous value, or -1 for an unknown key. */
 int bb_set_tuning(int key, int value);
 /* Test hook: the k-th interrupt poll from now reports an interrupt (k >= 0; -1 clears). */

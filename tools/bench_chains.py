@@ -21,6 +21,15 @@ call of the same build at K = CUs and 4 CUs into profiles/chains_summary_{c1,db}
 call, the trace call, the kernel-only rate, and the share of the summary call's runtime that
 k_trace_summary takes (timed alone on a full ring of a ChainBatch, scaled to the call).
 
+--alpha measures alpha unknown (alpha = 0, sampled by MH) with the fused kernels sampling it
+(bb_set_tuning key 26, bb_small_mh.hip) at K = 1, 256 and 1024 into
+profiles/chains_alpha_{c1,db}.json: alternated within each round, the single call with the key
+on (k_small_chain_mh) and off (the general path), and per K the key-on batch and this tree's
+known-alpha batch, each as the call and kernel only.  The baseline a batch has to beat is
+bridge_reg_stb_chains(alpha = 0) without the key, K sequential general-path chains:
+--alpha --mode single [--tree DIR] measures it (on the parent checkout, say; fewer samples keep
+K = 1024 sequential chains affordable) as one JSON line, which --baseline FILE merges.
+
 --wide measures the wide fused chains (bb_set_tuning key 25, bb_wide.hip) at the published
 protocol's wider shapes, synthetic designs dbi (442 x 64) and bhi (506 x 103), into
 profiles/chains_wide_{dbi,bhi}.json: alternated within each round, the single call with the key
@@ -39,6 +48,8 @@ median over rounds is reported with the min and max beside it.
   python tools/bench_chains.py --method tri [--mode single --tree DIR]
   python tools/bench_chains.py --summary [--method tri] [--designs c1]
   python tools/bench_chains.py --wide [--designs dbi]
+  python tools/bench_chains.py --alpha --mode single --tree DIR --nsamp 100 --burn 50 > FILE
+  python tools/bench_chains.py --alpha --baseline FILE
 """
 import argparse
 import json
@@ -95,9 +106,9 @@ class Method:
         return (self.bb.bridge_reg_tri_chains_summary if self.tri
                 else self.bb.bridge_reg_stb_chains_summary)(y, X, **kw)
 
-    def config(self, n, p, cap=1):
+    def config(self, n, p, cap=1, true_alpha=0.5):
         return self.bb.EngineConfig(n=n, p=p, trace_capacity=cap, seed=SEED,
-                                    method=4 if self.tri else 0)
+                                    method=4 if self.tri else 0, true_alpha=true_alpha)
 
 
 def spread(v):
@@ -105,11 +116,11 @@ def spread(v):
     return {"median": float(np.median(v)), "min": float(v[0]), "max": float(v[-1])}
 
 
-def kernel_rate(me, X, y, K, nsamp, threads=0, block=50):
+def kernel_rate(me, X, y, K, nsamp, threads=0, block=50, true_alpha=0.5):
     """Sweeps/s of the batch kernel alone: blocks of `block` sweeps, no traces, one sync.
     threads: the triangle batch's instance (0: the one the batch selects)."""
     n, p = X.shape
-    b = me.bb.ChainBatch(me.config(n, p), K, X, y)
+    b = me.bb.ChainBatch(me.config(n, p, true_alpha=true_alpha), K, X, y)
     try:
         if threads:
             b.set_threads(threads)
@@ -323,9 +334,118 @@ def bench_wide(me, name, X, y, cus, args):
             "chains": rows, "kernels": kernels}
 
 
+ALPHA_KEY = 26  # bb_set_tuning: alpha sampled in the fused small chains (bb_small_mh.hip)
+
+
+def bench_alpha(me, name, X, y, cus, args):
+    """Alpha unknown (alpha = 0: sampled by MH) under key 26 against this tree's known-alpha
+    batch, alternated within each round; the key is set only around the calls it is measured in
+    and left off.  The sequential general-path fallback at the same K comes from --baseline."""
+    bb = me.bb
+    Ks = [k for k in (args.chains or [1, 256, 1024]) if k <= args.max_chains]
+    nsamp, burn = args.nsamp, args.burn
+
+    def call(on, fn):
+        old = bb.set_tuning(ALPHA_KEY, 1 if on else 0)
+        try:
+            bb.set_seed(SEED)
+            return fn()
+        finally:
+            bb.set_tuning(ALPHA_KEY, old)
+
+    call(1, lambda: me.chains(y, X, nsamp=200, nchains=2, burn=100, alpha=0.0))  # warm-up
+    call(1, lambda: me.single(y, X, nsamp=200, burn=100, alpha=0.0))
+    call(0, lambda: me.single(y, X, nsamp=200, burn=100, alpha=0.0))
+    call(0, lambda: me.chains(y, X, nsamp=200, nchains=2, burn=100))
+    keys = ("mh", "mh_kernel", "known", "known_kernel")
+    v = {K: {k: [] for k in keys} for K in Ks}
+    one_fused, one_general, res = [], [], {}
+    for _ in range(args.reps):
+        one_fused.append(nsamp / call(1, lambda: me.single(y, X, nsamp=nsamp, burn=burn,
+                                                           alpha=0.0))["runtime"])
+        one_general.append(nsamp / call(0, lambda: me.single(y, X, nsamp=nsamp, burn=burn,
+                                                             alpha=0.0))["runtime"])
+        for K in Ks:
+            out = call(1, lambda: me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn, alpha=0.0))
+            v[K]["mh"].append(K * nsamp / out["runtime"])
+            del out
+            kr, res[K] = call(1, lambda: kernel_rate(me, X, y, K, nsamp, true_alpha=0.0))
+            v[K]["mh_kernel"].append(kr)
+            out = call(0, lambda: me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn))
+            v[K]["known"].append(K * nsamp / out["runtime"])
+            del out
+            v[K]["known_kernel"].append(call(0, lambda: kernel_rate(me, X, y, K, nsamp))[0])
+    base = {}
+    if args.baseline:
+        with open(args.baseline) as f:
+            for line in f:
+                if line.startswith("{"):
+                    rec = json.loads(line)
+                    base.update(rec.get("fallback_chains_sweeps_per_s", {}).get(name, {}))
+                    base_meta = {k: rec.get(k) for k in ("source_sha", "nsamp", "burn", "reps")}
+    rows = []
+    for K in Ks:
+        s = {k: spread(v[K][k]) for k in keys}
+        row = {"chains": K, "resident_per_cu": res[K],
+               "alpha_sampled_call_sweeps_per_s": s["mh"],
+               "alpha_sampled_kernel_sweeps_per_s": s["mh_kernel"],
+               "alpha_known_call_sweeps_per_s": s["known"],
+               "alpha_known_kernel_sweeps_per_s": s["known_kernel"],
+               "sampled_vs_known_call": s["mh"]["median"] / s["known"]["median"],
+               "sampled_vs_known_kernel": s["mh_kernel"]["median"] / s["known_kernel"]["median"]}
+        fb = base.get(str(K))
+        if fb:
+            row["fallback_general_path_sweeps_per_s"] = fb
+            row["vs_fallback"] = s["mh"]["median"] / fb["median"]
+            row["beats_fallback_beyond_spread"] = s["mh"]["min"] > fb["max"]
+        rows.append(row)
+    from bayesbridge_amd import _kernel_code
+
+    lanes = "512, 64, 16" if X.shape[1] <= 8 else "512, 32, 8" if X.shape[1] <= 16 else "512, 16, 8"
+    kernels = {k: {"code_sha": _kernel_code.code_sha(k)}
+               for k in (f"bb::k_small_chain_mh<{lanes}>", f"bb::k_small_chains_mh<{lanes}>",
+                         f"bb::k_small_chains<{lanes}>")}
+    f1, g1 = spread(one_fused), spread(one_general)
+    rec = {"design": name, "n": int(X.shape[0]), "p": int(X.shape[1]), "nsamp": nsamp,
+           "burn": burn, "reps": args.reps, "compute_units": cus,
+           "single_call_fused_sweeps_per_s": f1, "single_call_general_path_sweeps_per_s": g1,
+           "single_fused_vs_general_path": f1["median"] / g1["median"],
+           "chains": rows, "kernels": kernels}
+    if base:
+        rec["fallback_measured_with"] = base_meta
+    return rec
+
+
+def bench_alpha_fallback(me, args):
+    """bridge_reg_stb_chains(alpha = 0) with every key as the checkout has it (one JSON line):
+    on a checkout without key 26, or with it off, K sequential general-path chains -- the
+    baseline of --alpha, through --baseline."""
+    out = {}
+    for name, (X, y) in designs().items():
+        if name not in args.designs.split(","):
+            continue
+        me.bb.set_seed(SEED)
+        me.chains(y, X, nsamp=50, nchains=2, burn=20, alpha=0.0)
+        out[name] = {}
+        for K in args.chains or [1, 256, 1024]:
+            v = []
+            for _ in range(args.reps):
+                me.bb.set_seed(SEED)
+                r = me.chains(y, X, nsamp=args.nsamp, nchains=K, burn=args.burn, alpha=0.0)
+                v.append(K * args.nsamp / r["runtime"])
+                del r
+            out[name][str(K)] = spread(v)
+            print(f"{name} K={K:5d} fallback {out[name][str(K)]}", file=sys.stderr, flush=True)
+    print(json.dumps({"source_sha": me.bb._build.source_sha(), "nsamp": args.nsamp,
+                      "burn": args.burn, "reps": args.reps,
+                      "fallback_chains_sweeps_per_s": out}), flush=True)
+
+
 def bench_single(me, args):
     """The single-chain call alone at both designs (one JSON line): the A/B against another
     checkout."""
+    if args.alpha:
+        return bench_alpha_fallback(me, args)
     out = {}
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
@@ -359,8 +479,12 @@ def main():
                     help="the summary mode against the trace call (profiles/chains_summary_*)")
     ap.add_argument("--wide", action="store_true",
                     help="the wide fused chains (key 25) at dbi / bhi (profiles/chains_wide_*)")
+    ap.add_argument("--alpha", action="store_true",
+                    help="alpha unknown under key 26 (profiles/chains_alpha_*)")
+    ap.add_argument("--baseline", default=None,
+                    help="--alpha: the JSON line of an --alpha --mode single run to merge")
     ap.add_argument("--chains", type=lambda v: [int(t) for t in v.split(",")], default=None,
-                    help="--summary: the batch sizes (default CUs,4 CUs)")
+                    help="--summary: the batch sizes (default CUs,4 CUs); --alpha: 1,256,1024")
     ap.add_argument("--tag", default="", help="suffix of the output files' names")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
@@ -383,6 +507,27 @@ def main():
            else int(torch.cuda.get_device_properties(0).multi_processor_count))
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
+            continue
+        if args.alpha:
+            rec = bench_alpha(me, name, X, y, cus, args)
+            rec["source_sha"] = bb._build.source_sha()
+            with open(os.path.join(args.out_dir, f"chains_alpha_{name}{args.tag}.json"), "w") as f:
+                json.dump(rec, f, indent=1)
+                f.write("\n")
+            f1, g1 = rec["single_call_fused_sweeps_per_s"], rec["single_call_general_path_sweeps_per_s"]
+            print(f"{name} single call, alpha sampled: general path {g1['median']:.0f} sweeps/s "
+                  f"[{g1['min']:.0f}, {g1['max']:.0f}]  fused {f1['median']:.0f} "
+                  f"[{f1['min']:.0f}, {f1['max']:.0f}]  "
+                  f"x{rec['single_fused_vs_general_path']:.2f}", flush=True)
+            for r in rec["chains"]:
+                a, k = r["alpha_sampled_call_sweeps_per_s"], r["alpha_sampled_kernel_sweeps_per_s"]
+                fb = r.get("fallback_general_path_sweeps_per_s")
+                print(f"{name} K={r['chains']:5d} alpha sampled {a['median']:.0f} sweeps/s "
+                      f"[{a['min']:.0f}, {a['max']:.0f}]  kernel {k['median']:.0f}  "
+                      f"x{r['sampled_vs_known_call']:.2f} known alpha (kernel "
+                      f"x{r['sampled_vs_known_kernel']:.2f})"
+                      + (f"  x{r['vs_fallback']:.0f} fallback {fb['median']:.0f}" if fb else "")
+                      + f"  resident/CU {r['resident_per_cu']}", flush=True)
             continue
         if args.wide:
             rec = bench_wide(me, name, X, y, cus, args)

@@ -2,7 +2,8 @@
 // one launch of `count` sweeps on a synthetic n x p Gaussian design; prints the kernel time
 // per sweep and the split between S_alpha/rss, tau/sig2, lambda and beta.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DBB_SMALL_PHASES \
-//         -I bayesbridge_amd/csrc tools/small_phase_bench.cpp bayesbridge_amd/csrc/bb_small.hip
+//         -I bayesbridge_amd/csrc tools/small_phase_bench.cpp bayesbridge_amd/csrc/bb_small.hip \
+//         bayesbridge_amd/csrc/bb_small_mh.hip
 #include <hip/hip_runtime.h>
 
 #include <cmath>

@@ -13,7 +13,8 @@ what it returned (tests/test_ref_pin_cpu.py, bit for bit).  Everyt
 the reference's ``Matrix.h`` (tau, sig2, alpha, the beta maps, the triangle sampler, EM) is
 PARITY UNPINNED against reference outputs -- that header needs a whole matrix library -- and
 pinned instead by Philox KATs, numpy's Philox, analytic moments of the tilted stable law
-and exact-posterior quadrature (tests/test_oracle_cpu.py).
+and exact-posterior quadrature (tests/test_oracle_cpu.py); tests/test_posterior_law_cpu.py
+holds whole chains, alpha sampled included, to the model's posterior laws.
 """
 from __future__ import annotations
 

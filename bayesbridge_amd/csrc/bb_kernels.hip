@@ -28,6 +28,7 @@
 #include "bb_kernels.h"
 #include "bb_pg.h"
 #include "bb_sampler.h"
+#include "bb_wave.h"
 
 namespace bb {
 
@@ -36,21 +37,17 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------
 // reductions (deterministic: fixed tree per launch geometry)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
+// shfl_down tree: the wave's sum lands in lane 0 alone (bb_wave.h's wave_sum_all is the xor
+// tree that leaves it in every lane -- another order of additions, other bits)
+__device__ __forceinline__ double wave_sum_lane0(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;  // lane 0
 }
 
-__device__ __forceinline__ double wave_allsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int NT>
 __device__ __forceinline__ double block_sum(double v, double *sh) {
-    v = wave_sum(v);
+    v = wave_sum_lane0(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) sh[w] = v;
     __syncthreads();
@@ -1208,7 +1205,7 @@ constexpr int kEmCgThreads = 1024;
 __device__ double em_block_dot(const double *u, const double *v, int n, double *sh) {
     double a = 0.0;
     for (int i = threadIdx.x; i < n; i += kEmCgThreads) a += u[i] * v[i];
-    a = wave_allsum(a);
+    a = wave_sum_all(a);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) sh[w] = a;
@@ -1707,13 +1704,6 @@ __device__ __forceinline__ double fast_rcp(double p) {
     return __builtin_fma(r, __builtin_fma(-p, r, 1.0), r);
 }
 
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // ---------------------------------------------------------------------------
 // Persistent dataflow Cholesky: ONE launch factors the whole matrix.
 //   workgroup 0 (the chain) owns the critical path: for k = 0 .. nblk-1 it eliminates the
@@ -1926,12 +1916,12 @@ __device__ __forceinline__ void elim_produce(double (&a)[8][2], double (*ROWS)[1
 #pragma unroll
     for (int ci = 0; ci < 8; ++ci) {
         const int c = 8 * W + ci;
-        const double pv = readlane_d(a[ci][ci & 1], 4 * W + (ci >> 1));
+        const double pv = readlane_f64(a[ci][ci & 1], 4 * W + (ci >> 1));
         const double inv = fast_rcp(pv);
         const double rs0 = a[ci][0] * inv, rs1 = a[ci][1] * inv;
 #pragma unroll
         for (int i = ci + 1; i < 8; ++i) {
-            const double m = readlane_d(a[ci][i & 1], 4 * W + (i >> 1));
+            const double m = readlane_f64(a[ci][i & 1], 4 * W + (i >> 1));
             a[i][0] = __builtin_fma(-m, rs0, a[i][0]);
             a[i][1] = __builtin_fma(-m, rs1, a[i][1]);
         }
@@ -2110,12 +2100,12 @@ __device__ __forceinline__ void elim_produce2(double (&a)[8][2], double (*ROWS)[
 #pragma unroll
     for (int ci = 0; ci < 8; ++ci) {
         const int c = 8 * W + ci;
-        const double pv = readlane_d(a[ci][ci & 1], 4 * W + (ci >> 1));
+        const double pv = readlane_f64(a[ci][ci & 1], 4 * W + (ci >> 1));
         const double inv = fast_rcp(pv);
         const double rs0 = a[ci][0] * inv, rs1 = a[ci][1] * inv;
 #pragma unroll
         for (int i = ci + 1; i < 8; ++i) {
-            const double m = readlane_d(a[ci][i & 1], 4 * W + (i >> 1));
+            const double m = readlane_f64(a[ci][i & 1], 4 * W + (i >> 1));
             a[i][0] = __builtin_fma(-m, rs0, a[i][0]);
             a[i][1] = __builtin_fma(-m, rs1, a[i][1]);
         }
@@ -3108,7 +3098,7 @@ __global__ __launch_bounds__(256) void k_beta_wb(const double *__restrict__ X, i
             s += x.x * ws[r];
             s += x.y * ws[r + 1];
         }
-        s = wave_allsum(s);
+        s = wave_sum_all(s);
         if (lane == 0) {
             const double b = u[j] + D[j] * s / sig;
             beta[j] = b;
@@ -3177,7 +3167,7 @@ __global__ __launch_bounds__(64 * kBxbWaves, 1) void k_beta_wb_xb(
             s += xc[i].x * ws[128 * i + 2 * lane];
             s += xc[i].y * ws[128 * i + 2 * lane + 1];
         }
-        s = wave_allsum(s);
+        s = wave_sum_all(s);
         const double bj = ud.x + ud.y * s / sig;
         if (lane == 0) {
             beta[j] = bj;
@@ -3308,7 +3298,7 @@ __global__ __launch_bounds__(64 * kBxbWaves, 1) void k_beta_wb32(
             s0 = __builtin_fma((double)xc[i].x, wv.x, s0);
             s1 = __builtin_fma((double)xc[i].y, wv.y, s1);
         }
-        const double s = wave_allsum(s0 + s1);
+        const double s = wave_sum_all(s0 + s1);
         if (lane == 0) {
             const double bj = cj.u + cj.D * (cj.g + s) / sig;
             beta[j] = bj;
@@ -3404,19 +3394,25 @@ void launch_beta_ortho(hipStream_t s, const double *gdiag, const double *c, cons
                                                  beta_trace);
 }
 
-// alpha | beta, tau: BridgeRegression.cpp:469-503 (single workgroup).
+// The alpha MH step (bb_sampler.h: alpha_propose, alpha_mh_accept).  The proposal of sweep t
+// from the shared counter (every shard of a chain proposes the same alpha_new): a_new, its
+// window's width d_new and the uniform u1 of the decision.
+__device__ __forceinline__ double alpha_proposal(double a_old, Key key, uint64_t t, double &d_new,
+                                                 double &u1) {
+    const U4 u = uniforms(key, t, KIND_ALPHA, 0, 0, 0);
+    u1 = u.r[1];
+    return alpha_propose(a_old, u.r[0], d_new);
+}
+
+// alpha | beta, tau in a single workgroup.
 __global__ __launch_bounds__(1024) void k_alpha_mh(const double *beta, int p, DevScalars *sc,
                                                    double pr_a, double pr_b, Key key,
                                                    uint64_t t, double *alpha_tr) {
     __shared__ double sh[16];
     const double tau = sc->tau;
     const double a_old = sc->alpha;
-    const double ep = 0.1;
-    U4 u = uniforms(key, t, KIND_ALPHA, 0, 0, 0);
-    const double l_new = fmax(0.0, a_old - ep);
-    const double r_new = fmin(1.0, a_old + ep);
-    const double d_new = r_new - l_new;
-    const double a_new = l_new + d_new * u.r[0];
+    double d_new, u1;
+    const double a_new = alpha_proposal(a_old, key, t, d_new, u1);
     double sn = 0.0, so = 0.0;
     for (int i = threadIdx.x; i < p; i += 1024) {
         const double si = log(fabs(beta[i] / tau));
@@ -3426,18 +3422,9 @@ __global__ __launch_bounds__(1024) void k_alpha_mh(const double *beta, int p, De
     const double Sn = block_sum<1024>(sn, sh);
     const double So = block_sum<1024>(so, sh);
     if (threadIdx.x == 0) {
-        const double pp = (double)p;
-        const double llh_new = pp * log(a_new) - pp * lgamma(1.0 / a_new) - Sn;
-        const double llh_old = pp * log(a_old) - pp * lgamma(1.0 / a_old) - So;
         const double lbc = lgamma(pr_a) + lgamma(pr_b) - lgamma(pr_a + pr_b);
-        const double ldb_new = (pr_a - 1.0) * log(a_new) + (pr_b - 1.0) * log(1.0 - a_new) - lbc;
-        const double ldb_old = (pr_a - 1.0) * log(a_old) + (pr_b - 1.0) * log(1.0 - a_old) - lbc;
-        const double l_old = fmax(0.0, a_new - ep);
-        const double r_old = fmin(1.0, a_new + ep);
-        const double d_old = r_old - l_old;
-        const double log_accept = llh_new - llh_old + ldb_new - ldb_old + log(d_old) - log(d_new);
-        double an = a_new;
-        if (u.r[1] > exp(log_accept)) an = a_old;
+        const double an =
+            alpha_mh_accept(a_old, a_new, d_new, Sn, So, (double)p, pr_a, pr_b, lbc, u1);
         sc->alpha = an;
         if (alpha_tr) *alpha_tr = an;
     }
@@ -3448,28 +3435,17 @@ void launch_alpha_mh(hipStream_t s, const double *beta, int p, DevScalars *sc, d
     k_alpha_mh<<<1, 1024, 0, s>>>(beta, p, sc, pr_a, pr_b, Key{k0, k1}, t, alpha_tr);
 }
 
-// The same MH step for a column-sharded chain, split around an exchange: k_alpha_sums writes
-// this shard's [S(alpha_new), S(alpha_old)], S(a) = sum_j exp(a log|beta_j / tau|) (the
-// proposal comes from the shared counter, so every shard proposes the same alpha_new); the
-// caller sums the pairs over shards; k_alpha_decide evaluates llh_alpha_marg with the
-// GLOBAL p and accepts or rejects (BridgeRegression.cpp:469-503).  One shard gives the bits
-// of k_alpha_mh (same loop, tree and expressions).
-__device__ __forceinline__ double alpha_proposal(double a_old, Key key, uint64_t t, double &u1) {
-    const U4 u = uniforms(key, t, KIND_ALPHA, 0, 0, 0);
-    u1 = u.r[1];
-    const double ep = 0.1;
-    const double l_new = fmax(0.0, a_old - ep);
-    const double r_new = fmin(1.0, a_old + ep);
-    return l_new + (r_new - l_new) * u.r[0];
-}
-
+// The same step for a column-sharded chain, split around an exchange: k_alpha_sums writes this
+// shard's [S(alpha_new), S(alpha_old)]; the caller sums the pairs over shards; k_alpha_decide
+// decides with the GLOBAL p.  One shard gives the bits of k_alpha_mh (same loop, tree and
+// functions).
 __global__ __launch_bounds__(1024) void k_alpha_sums(const double *beta, int p_loc,
                                                      const DevScalars *sc, Key key, uint64_t t,
                                                      double *sums) {
     __shared__ double sh[16];
     const double tau = sc->tau, a_old = sc->alpha;
-    double u1;
-    const double a_new = alpha_proposal(a_old, key, t, u1);
+    double d_new, u1;
+    const double a_new = alpha_proposal(a_old, key, t, d_new, u1);
     double sn = 0.0, so = 0.0;
     for (int i = threadIdx.x; i < p_loc; i += 1024) {
         const double si = log(fabs(beta[i] / tau));
@@ -3487,22 +3463,12 @@ __global__ __launch_bounds__(1024) void k_alpha_sums(const double *beta, int p_l
 __global__ void k_alpha_decide(const double *sums, int p, DevScalars *sc, double pr_a,
                                double pr_b, Key key, uint64_t t, double *alpha_tr) {
     if (threadIdx.x != 0) return;
-    const double a_old = sc->alpha, ep = 0.1;
-    double u1;
-    const double a_new = alpha_proposal(a_old, key, t, u1);
-    const double d_new = fmin(1.0, a_old + ep) - fmax(0.0, a_old - ep);
-    const double pp = (double)p;
-    const double llh_new = pp * log(a_new) - pp * lgamma(1.0 / a_new) - sums[0];
-    const double llh_old = pp * log(a_old) - pp * lgamma(1.0 / a_old) - sums[1];
+    const double a_old = sc->alpha;
+    double d_new, u1;
+    const double a_new = alpha_proposal(a_old, key, t, d_new, u1);
     const double lbc = lgamma(pr_a) + lgamma(pr_b) - lgamma(pr_a + pr_b);
-    const double ldb_new = (pr_a - 1.0) * log(a_new) + (pr_b - 1.0) * log(1.0 - a_new) - lbc;
-    const double ldb_old = (pr_a - 1.0) * log(a_old) + (pr_b - 1.0) * log(1.0 - a_old) - lbc;
-    const double l_old = fmax(0.0, a_new - ep);
-    const double r_old = fmin(1.0, a_new + ep);
-    const double d_old = r_old - l_old;
-    const double log_accept = llh_new - llh_old + ldb_new - ldb_old + log(d_old) - log(d_new);
-    double an = a_new;
-    if (u1 > exp(log_accept)) an = a_old;
+    const double an =
+        alpha_mh_accept(a_old, a_new, d_new, sums[0], sums[1], (double)p, pr_a, pr_b, lbc, u1);
     sc->alpha = an;
     if (alpha_tr) *alpha_tr = an;
 }
@@ -3606,7 +3572,7 @@ __global__ __launch_bounds__(256) void k_coldot(const double *__restrict__ X, in
             s += x.x * v[r];
             s += x.y * v[r + 1];
         }
-        s = wave_allsum(s);
+        s = wave_sum_all(s);
         if (lane == 0) out[j] = s;
     }
 }
@@ -3633,7 +3599,7 @@ __global__ __launch_bounds__(256) void k_colnorm2(const double *__restrict__ X, 
             s += x.x * x.x;
             s += x.y * x.y;
         }
-        s = wave_allsum(s);
+        s = wave_sum_all(s);
         if (lane == 0) out[j] = s;
     }
 }

@@ -29,6 +29,7 @@
 
 #include "bb_kernels.h"
 #include "bb_sampler.h"
+#include "bb_wave.h"
 
 namespace bb {
 
@@ -39,12 +40,6 @@ __device__ inline double cheb_rho(double sigma1, int j) {
     double rho = 1.0 / sigma1;
     for (int i = 1; i <= j; ++i) rho = 1.0 / (2.0 * sigma1 - rho);
     return rho;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 }  // namespace
@@ -293,7 +288,7 @@ __global__ __launch_bounds__(kNidSumWG) void k_nid_sums(const double *__restrict
             if (dj > thr[k]) acc[k] += v;
     }
 #pragma unroll
-    for (int k = 0; k <= kNidTS; ++k) acc[k] = wave_sum(acc[k]);
+    for (int k = 0; k <= kNidTS; ++k) acc[k] = wave_sum_all(acc[k]);
     if (lane == 0)
 #pragma unroll
         for (int k = 0; k <= kNidTS; ++k) part[wid][k] = acc[k];
@@ -648,7 +643,7 @@ __device__ __forceinline__ void eapply_body(const T *__restrict__ X, int ldx, in
             double a = 0.0;
 #pragma unroll
             for (int m = 0; m < NR; ++m) a = __builtin_fma(xv[c][m], vr[m], a);
-            s[c] = wave_sum(a);
+            s[c] = wave_sum_all(a);
         }
         __syncthreads();  // the previous chunk's ws reads are done
         if (lane == 0)
@@ -766,7 +761,7 @@ __global__ __launch_bounds__(256) void k_sp_eapply_rows(const int *__restrict__ 
     if (row >= n_pad) return;
     double a = 0.0;
     for (int k = rowptr[row] + lane; k < rowptr[row + 1]; k += 64) a += rval[k] * s[colidx[k]];
-    a = wave_sum(a);
+    a = wave_sum_all(a);
     if (lane == 0) out[row] = a;
 }
 

@@ -10,6 +10,7 @@
 
 #include "bb_kernels.h"
 #include "bb_ozaki.h"
+#include "bb_wave.h"
 
 namespace bb {
 
@@ -231,13 +232,6 @@ void launch_oz_scale(hipStream_t s, const double *D, int p_pad, const double *xm
 // the low word of r + magic.  Stores: four 16-byte units per lane into the blocked layout
 // (16 consecutive lanes write one contiguous 256 B run), 4 KB per wave and modulus.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double oz_readlane_d(double v, int lane) {
-    const long long bits = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)bits, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(bits >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 constexpr int kOzResCols = 32;   // columns per wave (half a chunk): keeps occupancy >= 4
 constexpr int kOzResChunks = 4;  // 64-column chunks per workgroup, at most (oz_res_cpw)
 
@@ -278,10 +272,10 @@ __global__ __launch_bounds__(512) void k_oz_residues(const double *__restrict__ 
             v[j] = NTL ? __builtin_nontemporal_load(xp + (size_t)j * ldx) : xp[(size_t)j * ldx];
         if (u) {
 #pragma unroll
-            for (int j = 0; j < kOzResCols; ++j) xu += v[j] * oz_readlane_d(ul, j);
+            for (int j = 0; j < kOzResCols; ++j) xu += v[j] * readlane_f64(ul, j);
         }
 #pragma unroll
-        for (int j = 0; j < kOzResCols; ++j) v[j] = rint(v[j] * oz_readlane_d(sdl, j) * rsl);
+        for (int j = 0; j < kOzResCols; ++j) v[j] = rint(v[j] * readlane_f64(sdl, j) * rsl);
         // low 32 bits of each integer x (|x| <= 2^53): x = xh 2^32 + xl, 0 <= xl < 2^32
         unsigned int xl[kOzResCols];
 #pragma unroll

@@ -138,6 +138,42 @@ __device__ inline double gamma1(double shape, Key key, uint64_t t, unsigned kind
 }
 
 // ---------------------------------------------------------------------------
+// alpha | beta, tau: the random-walk MH step of sample_alpha_marg, BridgeRegression.cpp:478-503.
+// Every kernel that samples alpha (k_alpha_mh, k_alpha_sums / k_alpha_decide, the fused small
+// chains) proposes and decides through these two functions.
+// ---------------------------------------------------------------------------
+// The proposal (:485-488): a_new = l + d_new u0 in the window [l, r] = [max(0, a_old - 0.1),
+// min(1, a_old + 0.1)] of width d_new.
+__device__ __forceinline__ double alpha_propose(double a_old, double u0, double &d_new) {
+    const double ep = 0.1;
+    const double l_new = fmax(0.0, a_old - ep);
+    const double r_new = fmin(1.0, a_old + ep);
+    d_new = r_new - l_new;
+    return l_new + d_new * u0;
+}
+
+// The decision (:490-502) from Sn = S(a_new) and So = S(a_old), S(a) = sum_j exp(a log|beta_j /
+// tau|), over pp coefficients under the prior Beta(pr_a, pr_b), lbc = log B(pr_a, pr_b): the
+// alpha the chain goes on with.  :498 adds log(d_old) - log(d_new); the Hastings correction of
+// the window proposal is the opposite sign.  Kept as the reference has it (.C parity): the step
+// is exactly invariant for pi(alpha | .) d(alpha)^2, which is what the posterior-law tests hold
+// it to.
+__device__ __forceinline__ double alpha_mh_accept(double a_old, double a_new, double d_new,
+                                                  double Sn, double So, double pp, double pr_a,
+                                                  double pr_b, double lbc, double u1) {
+    const double ep = 0.1;
+    const double llh_new = pp * log(a_new) - pp * lgamma(1.0 / a_new) - Sn;
+    const double llh_old = pp * log(a_old) - pp * lgamma(1.0 / a_old) - So;
+    const double ldb_new = (pr_a - 1.0) * log(a_new) + (pr_b - 1.0) * log(1.0 - a_new) - lbc;
+    const double ldb_old = (pr_a - 1.0) * log(a_old) + (pr_b - 1.0) * log(1.0 - a_old) - lbc;
+    const double l_old = fmax(0.0, a_new - ep);
+    const double r_old = fmin(1.0, a_new + ep);
+    const double d_old = r_old - l_old;
+    const double log_accept = llh_new - llh_old + ldb_new - ldb_old + log(d_old) - log(d_new);
+    return u1 > exp(log_accept) ? a_old : a_new;
+}
+
+// ---------------------------------------------------------------------------
 // Tilted positive stable law, Code/C/retstable.cpp.
 // ---------------------------------------------------------------------------
 // The sampler's logarithms and sines, restricted to the arguments it produces, in straight-line

@@ -13,7 +13,8 @@
 // with the same counters as the general path (t = t0 + k per sweep), so both draw the same
 // chain up to summation order.  alpha known, or (the *_mh instances; opt-in, bb_set_tuning
 // key 26; bb_small_mh.hip) sampled by the reference's random-walk MH step after beta:
-//   alpha | beta, tau                :469-503 (sums in wave 0, the decision in thread 0)
+//   alpha | beta, tau                :469-503 (sums in wave 0, the decision in thread 0:
+//                                    bb_sampler.h's alpha_propose and alpha_mh_accept)
 #include <hip/hip_runtime.h>
 
 #include "bb_kernels.h"

@@ -1,12 +1,14 @@
 // bb_small_body.h -- the sweep loop of the fused small-p chain (bb_small.hip's header comment),
 // shared by its two translation units: bb_small.hip (alpha known) and bb_small_mh.hip (alpha
 // sampled).  They are two code objects, so that the out-of-line MH decision below is no part of
-// the known-alpha kernels' code identity (bayesbridge_amd/_kernel_code.py).
+// the known-alpha kernels' code identity (bayesbridge_amd/_kernel_code.py).  The sweep's first
+// steps (sums, tau and sig2, lambda, the orthogonal beta) are bb_chain_steps.h's, shared with
+// the wide and the triangle chains; the look-ahead, the factor and solves and the MH step are
+// here.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "bb_kernels.h"
-#include "bb_sampler.h"
+#include "bb_chain_steps.h"
 
 namespace bb {
 
@@ -16,36 +18,13 @@ constexpr int kSmallMaxP = kSmallChainMaxP;
 constexpr size_t kSmallXLds = 112 * 1024;  // X staged in LDS up to this size
 constexpr int kSmallPre = 32;  // sweeps of counter-only variates drawn ahead
 
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// The decision of the alpha MH step from the two sums S(a) = sum_j exp(a log|beta_j / tau|):
-// k_alpha_mh's expressions (BridgeRegression.cpp:469-503), lbc = log B(pr_a, pr_b).  One thread's
-// scalar work, kept out of line so that the sweep loop's registers are not its (inlined, the
-// MH instances spill 122-125 VGPRs and take 504-520 B of scratch per lane; so, 5-8 and 40-56).
+// alpha_mh_accept (bb_sampler.h) out of line: one thread's scalar work, whose registers are
+// then not the sweep loop's (inlined, the MH instances spill 122-125 VGPRs and take 504-520 B
+// of scratch per lane; so, 5-8 and 40-56).
 [[maybe_unused]] __device__ __noinline__ double alpha_mh_decide(double a_old, double a_new, double d_new,
                                                double Sn, double So, double pp, double pr_a,
                                                double pr_b, double lbc, double u1) {
-    const double ep = 0.1;
-    const double llh_new = pp * log(a_new) - pp * lgamma(1.0 / a_new) - Sn;
-    const double llh_old = pp * log(a_old) - pp * lgamma(1.0 / a_old) - So;
-    const double ldb_new = (pr_a - 1.0) * log(a_new) + (pr_b - 1.0) * log(1.0 - a_new) - lbc;
-    const double ldb_old = (pr_a - 1.0) * log(a_old) + (pr_b - 1.0) * log(1.0 - a_old) - lbc;
-    const double l_old = fmax(0.0, a_new - ep);
-    const double r_old = fmin(1.0, a_new + ep);
-    const double d_old = r_old - l_old;
-    const double log_accept = llh_new - llh_old + ldb_new - ldb_old + log(d_old) - log(d_new);
-    return u1 > exp(log_accept) ? a_old : a_new;
+    return alpha_mh_accept(a_old, a_new, d_new, Sn, So, pp, pr_a, pr_b, lbc, u1);
 }
 
 }  // namespace
@@ -63,9 +42,10 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 // it once, k_small_chains once per workgroup on that chain's state, so the arithmetic exists
 // once.
 // LOST: a chain whose state is no longer finite skips its lambda draws (k_small_chains).
-// MH: alpha is chain state (uniform over the workgroup in s_alpha), drawn after beta with the
-// counters and expressions of k_alpha_mh under the prior (pr_a, pr_b); tau's gamma variate,
-// whose shape then moves with alpha, is drawn in the sweep.
+// MH: alpha is chain state (uniform over the workgroup in s_alpha), drawn after beta with
+// k_alpha_mh's counters and the same two functions (bb_sampler.h: alpha_propose,
+// alpha_mh_accept) under the prior (pr_a, pr_b); tau's gamma variate, whose shape then moves
+// with alpha, is drawn in the sweep.
 template <int NT, int L, int I, bool LOST, bool MH = false>
 __device__ __forceinline__ void small_chain_body(
     const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
@@ -158,83 +138,27 @@ __device__ __forceinline__ void small_chain_body(
         // MH: the alpha of the previous sweep's step (written before that sweep's last barrier)
         double alpha = alpha0;
         if constexpr (MH) alpha = s_alpha;
-        // ---- S_alpha = sum |beta_j|^alpha and rss = |y - X beta|^2 ----
-        double sa = 0.0, rs = 0.0;
-        if (tid < p) sa = exp(alpha * log(fabs(sb[tid])));
-        for (int i = tid; i < n; i += NT) {
-            double xb = 0.0;
-            for (int j = 0; j < p; ++j) xb += Xs[(size_t)i + (size_t)j * lds_x] * sb[j];
-            const double r = y[i] - xb;
-            rs += r * r;
-        }
-        sa = wave_sum_all(sa);
-        rs = wave_sum_all(rs);
-        if (lane == 0) {
-            red[0][wid] = sa;
-            red[1][wid] = rs;
-        }
+        chain_sums<NT, NT>(Xs, lds_x, n, p, y, sb, alpha, red);
         __syncthreads();
         SMALL_PHASE(1);
-        // tau (wave 0) and sig2 (wave 1) are independent draws: BridgeRegression.cpp:453-465,
-        // :436-450
-        if (tid == 0 || tid == 64) {
-            double S = red[tid == 0 ? 0 : 1][0];
-#pragma unroll
-            for (int w = 1; w < NT / 64; ++w) S += red[tid == 0 ? 0 : 1][w];
-            if (tid == 0) {
-                if (!hy.know_tau) {
-                    double g;
-                    if constexpr (MH)
-                        g = gamma1(hy.nu_shape + ((double)p) / alpha, key, t, KIND_TAU, err);
-                    else
-                        g = s_gt[kp];
-                    const double nu = g / (hy.nu_rate + S);
-                    s_tau = exp(-1.0 * log(nu) / alpha);
-                }
-                if (slot >= 0) {
-                    tr_tau[slot] = s_tau;
-                    if constexpr (!MH) tr_alpha[slot] = alpha;
-                }
-            } else {
-                if (!hy.know_sig2) s_sig2 = (hy.sig2_scale + 0.5 * S) / s_gs[kp];
-                if (slot >= 0) tr_sig2[slot] = s_sig2;
-            }
-        }
+        // MH: tau's shape moves with alpha, so its gamma variate is drawn here
+        const auto tau_gamma = [&] {
+            if constexpr (MH)
+                return gamma1(hy.nu_shape + ((double)p) / alpha, key, t, KIND_TAU, err);
+            else
+                return s_gt[kp];
+        };
+        chain_scalars<NT, !MH>(red, hy, alpha, tau_gamma, &s_gs[kp], s_tau, s_sig2, slot, tr_tau,
+                               tr_sig2, tr_alpha);
         __syncthreads();
         SMALL_PHASE(2);
         const double tau = s_tau, sig2 = s_sig2;
-        // ---- lambda_j = 2 retstable(beta_j^2 / tau^2, alpha / 2, 1) ----
-        for (int jb = 0; jb < p; jb += NT / L) {
-            const int j = jb + tid / L;
-            const bool act = j < p;
-            const double b = act ? sb[j] : 0.0;
-            // A NaN tilt (the chain's state is no longer finite) fails every test of the
-            // rejection sampler, which then gives up after BB_MAX_STABLE_ROUNDS rounds --
-            // seconds per sweep -- with error bit 2 and a NaN draw.  A batch takes that outcome
-            // at once (LOST): a lost chain must not hold a CU that other chains wait for.
-            const double h = b * b / (tau * tau);
-            const bool lost = LOST && act && h != h;
-            double x = stable_spec_draw<L, I>(act && !lost, h, 0.5 * alpha, 1.0, key, t,
-                                              (uint64_t)j, err);
-            if (lost) {
-                x = __builtin_nan("");
-                if ((tid % L) == 0) atomicOr(err, 2u);
-            }
-            if (act && (tid % L) == 0) {
-                sl[j] = 2 * x;
-                if (slot >= 0) tr_lam[(size_t)slot * p + j] = 2 * x;
-            }
-        }
+        chain_lambda<NT, L, I, LOST>(p, sb, sl, tau, alpha, key, t, slot, tr_lam, err);
         __syncthreads();
         SMALL_PHASE(3);
         // ---- beta | rest ----
         if (ortho) {
-            if (tid < p) {  // BridgeRegression.cpp:514-521
-                const double uu = sgd[tid] + sl[tid] * sig2 / (tau * tau);
-                const double sd = sqrt(sig2 / uu);
-                const double m = sc_[tid] / uu;
-                sb[tid] = m + sd * s_z[kp][tid];
-            }
+            chain_beta_ortho(p, sb, sc_, sgd, sl, s_z[kp], tau, sig2);
         } else {
             // A = G + diag(lambda sig2 / tau^2), factored right-looking as A = U'U with one
             // thread per upper-triangle entry (i, j) (two for the last 16 at p = 32): per
@@ -303,11 +227,9 @@ __device__ __forceinline__ void small_chain_body(
         if constexpr (MH) {
             // ---- alpha | beta, tau: the lanes of wave 0 hold the beta they just wrote ----
             if (wid == 0) {
-                const double a_old = alpha, ep = 0.1;
-                const double l_new = fmax(0.0, a_old - ep);
-                const double r_new = fmin(1.0, a_old + ep);
-                const double d_new = r_new - l_new;
-                const double a_new = l_new + d_new * s_ua[kp][0];
+                const double a_old = alpha;
+                double d_new;
+                const double a_new = alpha_propose(a_old, s_ua[kp][0], d_new);
                 double sn = 0.0, so = 0.0;
                 if (lane < p) {
                     const double si = log(fabs(sb[lane] / tau));

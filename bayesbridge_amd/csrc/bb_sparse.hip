@@ -13,27 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "bb_sparse.h"
+#include "bb_wave.h"
 
 namespace bb {
-
-namespace {
-
-__device__ __forceinline__ double readlane_dbl(double v, int lane) {
-    const unsigned long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffu), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-template <int W>
-__device__ __forceinline__ double group_sum(double v) {
-    // xor tree inside aligned groups of W lanes; every lane of the group gets the sum
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // setup: pair list
@@ -123,7 +105,7 @@ __global__ __launch_bounds__(256) void k_sp_build(
             const int j = __builtin_amdgcn_readlane(jl, l);
             const int q0 = __builtin_amdgcn_readlane(q0l, l);
             const int q1 = __builtin_amdgcn_readlane(q1l, l);
-            const double xc = readlane_dbl(xl, l);
+            const double xc = readlane_f64(xl, l);
             for (int q = q0 + lane; q < q1; q += 64) {
                 const int r = rowidx[q];
                 const unsigned pos = cur[r];

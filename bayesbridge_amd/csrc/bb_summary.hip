@@ -24,6 +24,7 @@
 #include <stdexcept>
 
 #include "bb_kernels.h"
+#include "bb_wave.h"
 
 namespace bb {
 
@@ -32,13 +33,6 @@ namespace {
 constexpr int kSumTile = 8;                 // adjacent parameters (waves) of a workgroup
 constexpr int kSumChunk = kSummaryLanes;    // ring slots staged per pass: one per lane
 constexpr int kSumThreads = 64 * kSumTile;  // = kSumChunk * kSumTile: a thread per staged value
-
-__device__ __forceinline__ double readlane_sum(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 // lane k takes lane k - 1's v, lane 0 takes `in` (wave_shr:1 leaves lane 0 its old value)
 __device__ __forceinline__ double wave_shift_in(double v, double in) {
@@ -96,11 +90,11 @@ __global__ __launch_bounds__(kSumThreads) void k_trace_summary(
         if (!live) continue;
         const int t0 = s0 + base;
         const double xv = lane < n ? tile[lane][w] : 0.0;
-        if (t0 == 0) x0 = readlane_sum(xv, 0);
+        if (t0 == 0) x0 = readlane_f64(xv, 0);
         const double zv = xv - x0;
         if (t0 >= kSummaryMaxLag) {  // every lag has its partner: no head sums any more
             for (int i = 0; i < n; ++i) {
-                const double z = readlane_sum(zv, i);
+                const double z = readlane_f64(zv, i);
                 const int t = t0 + i;
                 W = wave_shift_in(W, z);
                 const double zw = z * W;
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(kSumThreads) void k_trace_summary(
             }
         } else {
             for (int i = 0; i < n; ++i) {
-                const double z = readlane_sum(zv, i);
+                const double z = readlane_f64(zv, i);
                 const int t = t0 + i;
                 W = wave_shift_in(W, z);
                 const double zw = z * W;
@@ -176,7 +170,7 @@ __global__ __launch_bounds__(256) void k_summary_finalise(
     const double m = T / dM;
     double tail = 0.0;  // the sum of the last `lane` values, newest first
     for (int j = 0; j < kSummaryMaxLag; ++j) {
-        const double wj = readlane_sum(W, j);
+        const double wj = readlane_f64(W, j);
         if (lane > j) tail += wj;
     }
     double v = 0.0;

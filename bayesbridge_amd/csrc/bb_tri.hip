@@ -20,8 +20,7 @@
 // uniform / translated-exponential proposal.  Counter kinds 8 (omega), 9 (u), 10 (z_i).
 #include <hip/hip_runtime.h>
 
-#include "bb_kernels.h"
-#include "bb_sampler.h"
+#include "bb_chain_steps.h"
 
 namespace bb {
 
@@ -38,13 +37,6 @@ constexpr unsigned KIND_TRI_OMEGA = 8, KIND_TRI_U = 9, KIND_TRI_Z = 10;
 struct Pre {
     double r0, r1, x0;
 };
-
-__device__ __forceinline__ double readlane_dd(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 __device__ __forceinline__ void attempt(Key key, uint64_t t, uint64_t i, uint64_t it, long k,
                                         const Pre &pre, double &r0, double &r1, double &x0,
@@ -165,7 +157,7 @@ __device__ __forceinline__ double tnorm_par(double lo, double hi, double mu, dou
         val = a > 0.0 ? mu + sd * x : mu - sd * x;
     }
     const uint64_t m = __ballot(acc && lane < K);
-    if (m) return readlane_dd(val, __ffsll((unsigned long long)m) - 1);
+    if (m) return readlane_f64(val, __ffsll((unsigned long long)m) - 1);
     return tnorm<LOST>(lo, hi, mu, sd, key, t, i, it, Pre{0.0, 0.0, 0.0}, err, K);
 }
 
@@ -195,19 +187,13 @@ __device__ __forceinline__ double row16_min(double v) {
 
 // Combine the four row extremes of a wave (every lane holds its row's value) through
 // scalar reads of lanes 0, 16, 32, 48: the wave's extreme, uniform in every lane.
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 __device__ __forceinline__ double rows_max(double v) {
-    return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)),
-                fmax(readlane_d(v, 32), readlane_d(v, 48)));
+    return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)),
+                fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
 __device__ __forceinline__ double rows_min(double v) {
-    return fmin(fmin(readlane_d(v, 0), readlane_d(v, 16)),
-                fmin(readlane_d(v, 32), readlane_d(v, 48)));
+    return fmin(fmin(readlane_f64(v, 0), readlane_f64(v, 16)),
+                fmin(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
 
 // tVc: tV column-major (tVc[i + j p] = tV(i, j)); tVr: its transpose (tVr[i p + j] =
@@ -448,12 +434,6 @@ constexpr int kTcK = 16;                // parallel truncated-normal attempts
 constexpr size_t kTcXLds = 96 * 1024;  // X staged in LDS up to this size
 constexpr int kTcP = kTriChainMaxP;
 
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // The counter-only variates of one sweep, in a buffer of tc_nvar(P) doubles laid out for P
 // coefficients (P = kTcP in the static buffers of the 512-thread instances, P = p in the
 // compact instance's dynamic LDS):
@@ -502,12 +482,12 @@ __device__ __forceinline__ void tc_variate(const TcVariates &v, int e, int p, do
 
 // The whole sweep loop of one chain in one workgroup: k_tri_chain runs it once, k_tri_chains
 // once per workgroup on that chain's state, so the arithmetic exists once.
+// The sums and the tau / sig2 draws are bb_chain_steps.h's (chain_sums, chain_scalars).
 // NT: real threads (64 | NT | kTcNT).  The only order-dependent arithmetic outside wave 0 is the
-// S_alpha / rss reduction over kTcNT threads; a narrower workgroup keeps kTcNT VIRTUAL threads,
-// real thread tid accumulating one separate partial for each virtual thread tid + q NT, so
-// every virtual wave lies in one real wave at the same lanes, its xor butterfly gives the same
-// bits and red[.][0..7] are summed in the same order.  The pre-drawn variates depend on their
-// counters alone, so which thread draws them does not matter.
+// S_alpha / rss reduction over kTcNT threads; a narrower workgroup keeps kTcNT VIRTUAL threads
+// (chain_sums<NT, kTcNT>), so red[.][0..7] hold the same bits and are summed in the same order.
+// The pre-drawn variates depend on their counters alone, so which thread draws them does not
+// matter.
 // COMPACT: the basis and the variate buffers live in the dynamic LDS behind X, sized by p
 // instead of kTcP, so that several workgroups share a CU's LDS.
 // LOST: a draw that can never be accepted gives up at once (tn_pos).
@@ -521,7 +501,6 @@ __device__ __forceinline__ void tri_chain_body(
     int first_slot, int slot_step, int cap, double *tr_beta, double *tr_u, double *tr_omega,
     double *tr_shape, double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err) {
     static_assert(NT % 64 == 0 && NT >= 128 && kTcNT % NT == 0, "NT divides kTcNT; wave 1 draws sig2");
-    constexpr int Q = kTcNT / NT;  // virtual threads per real thread
     extern __shared__ double sX[];
     __shared__ double sT[COMPACT ? 1 : 2 * kTcP * kTcP];
     __shared__ double sV[COMPACT ? 1 : 2 * tc_nvar(kTcP)];
@@ -568,46 +547,10 @@ __device__ __forceinline__ void tri_chain_body(
         const TcVariates v = vbuf(k & 1);
         const uint64_t t = t0 + (uint64_t)k;
         const int slot = first_slot < 0 ? -1 : (first_slot + k * slot_step) % cap;
-        // ---- S_alpha = sum |beta_j|^alpha and rss = |y - X beta|^2 ----
-        // (p <= 64: only virtual wave 0 holds terms of S_alpha, the others' sums are +0)
-        double sa = 0.0, rs[Q];
-        if (tid < p) sa = exp(alpha * log(fabs(sb[tid])));
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            rs[q] = 0.0;
-            for (int i = tid + q * NT; i < n; i += kTcNT) {
-                double xb = 0.0;
-                for (int j = 0; j < p; ++j) xb += Xs[(size_t)i + (size_t)j * lds_x] * sb[j];
-                const double r = y[i] - xb;
-                rs[q] += r * r;
-            }
-        }
-        sa = wave_sum64(sa);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            rs[q] = wave_sum64(rs[q]);
-            if (lane == 0) {
-                red[0][wid + q * (NT / 64)] = q == 0 ? sa : 0.0;
-                red[1][wid + q * (NT / 64)] = rs[q];
-            }
-        }
+        chain_sums<NT, kTcNT>(Xs, lds_x, n, p, y, sb, alpha, red);
         __syncthreads();
-        // tau | beta (wave 0) and sig2 | beta (wave 1), as k_scalars
-        if (tid == 0 || tid == 64) {
-            double S = red[tid == 0 ? 0 : 1][0];
-#pragma unroll
-            for (int w = 1; w < kTcNT / 64; ++w) S += red[tid == 0 ? 0 : 1][w];
-            if (tid == 0) {
-                if (!hy.know_tau) s_tau = exp(-1.0 * log(v.gt() / (hy.nu_rate + S)) / alpha);
-                if (slot >= 0) {
-                    tr_tau[slot] = s_tau;
-                    tr_alpha[slot] = alpha;
-                }
-            } else {
-                if (!hy.know_sig2) s_sig2 = (hy.sig2_scale + 0.5 * S) / v.gs();
-                if (slot >= 0) tr_sig2[slot] = s_sig2;
-            }
-        }
+        chain_scalars<kTcNT, true>(red, hy, alpha, [&] { return v.gt(); }, &v.gs(), s_tau, s_sig2,
+                                   slot, tr_tau, tr_sig2, tr_alpha);
         __syncthreads();
         if (wid > 0) {
             // the next sweep's variates, off wave 0's serial chain
@@ -654,10 +597,9 @@ __device__ __forceinline__ void tri_chain_body(
                 double bl = act ? sb[lane] : 0.0;
                 for (int j = 0; j < p; ++j) {
                     const double prod = (act && lane != j) ? sTc[j * p + lane] * bl : 0.0;
-                    const double xb = wave_sum64(prod);  // xor butterfly: the same bits in
-                                                          // every lane
-                    const double gjj = readlane_d(dj_c, j), bnd = readlane_d(bj, j);
-                    const double m = (readlane_d(aj_c, j) - xb) / gjj;
+                    const double xb = wave_sum_all(prod);  // xor tree: the same bits in every lane
+                    const double gjj = readlane_f64(dj_c, j), bnd = readlane_f64(bj, j);
+                    const double m = (readlane_f64(aj_c, j) - xb) / gjj;
                     const double sd = sqrt(sig2 / gjj);
                     const int ka = lane < kTcK ? lane : 0;
                     const double zn = tnorm_par<kTcK, LOST>(-1.0 * bnd, bnd, m, sd, v.r(j, ka, 0),
@@ -688,12 +630,12 @@ __device__ __forceinline__ void tri_chain_body(
                     for (int j = 0; j < p; ++j) zr += sTc[lane + j * p] * sb[j];
                 double bc = 0.0;
                 for (int kk = 0; kk < p; ++kk) {
-                    const double zk = readlane_d(zr, kk);
+                    const double zk = readlane_f64(zr, kk);
                     if (act) bc += sTr[kk * p + lane] * zk;
                 }
                 for (int i = 0; i < p; ++i) {  // :250-283
                     const double vi = act ? sTr[i * p + lane] : 0.0;
-                    const double zi = readlane_d(zr, i);
+                    const double zi = readlane_f64(zr, i);
                     double lmax = -1.0 * 1.7976931348623157e308, rmin = 1.7976931348623157e308;
                     if (act) {
                         const double rji = bc - vi * zi;
@@ -705,21 +647,21 @@ __device__ __forceinline__ void tri_chain_body(
                     }
                     const double L = rows_max(row16_max(lmax));
                     const double R = rows_min(row16_min(rmin));
-                    const double sdi = readlane_d(si, i);
+                    const double sdi = readlane_f64(si, i);
                     double zn;
                     if (it == 0) {
                         const int ka = lane < kTcK ? lane : 0;
                         if (sdi > 0.0)
-                            zn = tnorm_par<kTcK, LOST>(L, R, readlane_d(ci, i), sdi,
+                            zn = tnorm_par<kTcK, LOST>(L, R, readlane_f64(ci, i), sdi,
                                                        v.r(i, ka, 0), v.r(i, ka, 1), v.x(i, ka),
                                                        key, t, (uint64_t)i, 0, err);
                         else
                             zn = L + (R - L) * v.r(i, 0, 0);
                     } else {
-                        const Pre pi{readlane_d(pr.r0, i), readlane_d(pr.r1, i),
-                                     readlane_d(pr.x0, i)};
+                        const Pre pi{readlane_f64(pr.r0, i), readlane_f64(pr.r1, i),
+                                     readlane_f64(pr.x0, i)};
                         if (sdi > 0.0)
-                            zn = tnorm<LOST>(L, R, readlane_d(ci, i), sdi, key, t, (uint64_t)i,
+                            zn = tnorm<LOST>(L, R, readlane_f64(ci, i), sdi, key, t, (uint64_t)i,
                                              (uint64_t)it, pi, err);
                         else
                             zn = L + (R - L) * pi.r0;
@@ -730,7 +672,7 @@ __device__ __forceinline__ void tri_chain_body(
                 // beta = tV' z (:285)
                 double bn = 0.0;
                 for (int kk = 0; kk < p; ++kk) {
-                    const double zk = readlane_d(zr, kk);
+                    const double zk = readlane_f64(zr, kk);
                     if (act) bn += sTr[kk * p + lane] * zk;
                 }
                 if (act) sb[lane] = bn;

@@ -13,15 +13,19 @@
 //                                     MAXP / 64 entries per lane) or the orthogonal design's
 //                                     :514-521
 // with the counters of the general path (t = t0 + k per sweep), so both draw the same chain up
-// to summation order.  alpha known (the MH step runs on the general path).
+// to summation order.  alpha known (the MH step runs on the general path).  The sums and the
+// orthogonal beta draw are bb_chain_steps.h's, which leaves these kernels' code as it was.  The
+// tau / sig2 draws and the lambda draw are chain_scalars and chain_lambda written out: called
+// instead, the same arithmetic is scheduled otherwise, and the p <= 64 batch then ran 0.8-1.0 %
+// slower (lambda alone written out: 1.5-1.9 % slower; the scalars alone: the p <= 64 single
+// chain 2.4 % slower; the spread between rounds is 0.2-0.5 %).
 //
 // LDS: U alone, as its packed upper triangle of p (p + 1) / 2 doubles (dynamic: 66 KB at p =
 // 128); G is read-only and shared, so every sweep reads the owned entries of its upper triangle
 // through L2 straight into the registers the factor works in.
 #include <hip/hip_runtime.h>
 
-#include "bb_kernels.h"
-#include "bb_sampler.h"
+#include "bb_chain_steps.h"
 
 namespace bb {
 
@@ -29,19 +33,6 @@ namespace {
 
 constexpr int kWidePre = 16;  // sweeps of counter-only variates drawn ahead (16 KB at MAXP = 128)
 constexpr int kWideL = 16, kWideI = 8;  // lanes per coefficient of the lambda draw
-
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 // entry kk of a vector held as lane + 64 q in v[q] (kk uniform over the wave)
 template <int E>
@@ -119,24 +110,10 @@ __device__ __forceinline__ void wide_chain_body(
         const int kp = k % kWidePre;
         const uint64_t t = t0 + (uint64_t)k;
         const int slot = first_slot < 0 ? -1 : (first_slot + k * slot_step) % cap;
-        // ---- S_alpha = sum |beta_j|^alpha and rss = |y - X beta|^2 ----
-        double sa = 0.0, rs = 0.0;
-        if (tid < p) sa = exp(alpha * log(fabs(sb[tid])));
-        for (int i = tid; i < n; i += NT) {
-            double xb = 0.0;
-            for (int j = 0; j < p; ++j) xb += X[(size_t)i + (size_t)j * ldx] * sb[j];
-            const double r = y[i] - xb;
-            rs += r * r;
-        }
-        sa = wave_sum_all(sa);
-        rs = wave_sum_all(rs);
-        if (lane == 0) {
-            red[0][wid] = sa;
-            red[1][wid] = rs;
-        }
+        // X is read from memory: shared by every chain, L2-resident
+        chain_sums<NT, NT>(X, ldx, n, p, y, sb, alpha, red);
         __syncthreads();
-        // tau (wave 0) and sig2 (wave 1) are independent draws: BridgeRegression.cpp:453-465,
-        // :436-450
+        // tau (thread 0) and sig2 (thread 64): chain_scalars<NT, true>, written out (see above)
         if (tid == 0 || tid == 64) {
             double S = red[tid == 0 ? 0 : 1][0];
 #pragma unroll
@@ -157,15 +134,11 @@ __device__ __forceinline__ void wide_chain_body(
         }
         __syncthreads();
         const double tau = s_tau, sig2 = s_sig2;
-        // ---- lambda_j = 2 retstable(beta_j^2 / tau^2, alpha / 2, 1), NT / 16 a pass ----
+        // ---- lambda: chain_lambda<NT, kWideL, kWideI, LOST>, written out (see above) ----
         for (int jb = 0; jb < p; jb += NT / kWideL) {
             const int j = jb + tid / kWideL;
             const bool act = j < p;
             const double b = act ? sb[j] : 0.0;
-            // A NaN tilt (the chain's state is no longer finite) fails every test of the
-            // rejection sampler, which then gives up after BB_MAX_STABLE_ROUNDS rounds --
-            // seconds per sweep -- with error bit 2 and a NaN draw.  A batch takes that outcome
-            // at once (LOST): a lost chain must not hold a CU that other chains wait for.
             const double h = b * b / (tau * tau);
             const bool lost = LOST && act && h != h;
             double x = stable_spec_draw<kWideL, kWideI>(act && !lost, h, 0.5 * alpha, 1.0, key, t,
@@ -182,12 +155,7 @@ __device__ __forceinline__ void wide_chain_body(
         __syncthreads();
         // ---- beta | rest ----
         if (ortho) {
-            if (tid < p) {  // BridgeRegression.cpp:514-521
-                const double uu = sgd[tid] + sl[tid] * sig2 / (tau * tau);
-                const double sd = sqrt(sig2 / uu);
-                const double m = sc_[tid] / uu;
-                sb[tid] = m + sd * s_z[kp][tid];
-            }
+            chain_beta_ortho(p, sb, sc_, sgd, sl, s_z[kp], tau, sig2);
         } else {
             // A = G + diag(lambda sig2 / tau^2), read through L2 into the owners' registers and
             // factored right-looking as A = U'U: per pivot k the owner of (k, k) takes the

@@ -11,7 +11,6 @@ batch is bit for bit the c-th of K consecutive bridge_reg_stb calls.  The unequa
 (alpha_a, alpha_b) = (2, 3) tell the reference's (alpha_b, alpha_b) quirk of the non-orthogonal
 MCMC loop from (alpha_a, alpha_b).  Every test that sets the key restores it in a finally.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -22,6 +21,7 @@ from tests.conftest import synthetic_problem
 from tests.test_chains_gpu import (KEYS, assert_chain_equal, compare_chain, one_sweep,
                                    ortho_problem, sequential)
 from tests.test_summary_gpu import check_against_trace_call
+from tests.tuning import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -31,13 +31,8 @@ PRIOR = dict(alpha_a=2.0, alpha_b=3.0)
 MIN_MOVES = 10  # accepted, and rejected, proposals the oracle's alpha trace must hold
 
 
-@contextlib.contextmanager
 def fused_alpha(bb, on=True):
-    old = bb.set_tuning(ALPHA_KEY, 1 if on else 0)
-    try:
-        yield
-    finally:
-        bb.set_tuning(ALPHA_KEY, old)
+    return tuning(bb, ALPHA_KEY, 1 if on else 0)
 
 
 def assert_both_branches(alpha_trace, what):
@@ -294,25 +289,17 @@ def test_switch(gpu_lib):
         with fused_alpha(bb, False):
             rc, h, msg = create(bb.EngineConfig(n=80, p=12, true_alpha=0.0), 2, Xs)
             assert rc == -1 and not h and "bb_chains_create" in msg and "alpha" in msg, msg
-        old_wide = bb.set_tuning(25, 1)
-        try:
-            with fused_alpha(bb):
-                # 32 < p <= 128 and the triangle mixture: unchanged, whatever the keys
-                rc, h, msg = create(bb.EngineConfig(n=200, p=40, true_alpha=0.0), 2, X)
-                assert rc == -1 and not h and "alpha" in msg, msg
-                rc, h, msg = create(bb.EngineConfig(n=80, p=12, true_alpha=0.0, method=4), 2, Xs)
-                assert rc == -1 and not h and "alpha" in msg, msg
-        finally:
-            bb.set_tuning(25, old_wide)
-        old_packed = bb.set_tuning(21, 1)
-        try:
-            with fused_alpha(bb):
-                kept = fresh_batch(bb, Xs, y[:80], 2)
-                ref = fresh_batch(bb, Xs, y[:80], 2)
-                assert kept.threads() == 512 and kept.resident_per_cu() >= 1
-                tr_ref, st_ref = one_sweep(ref, 2)
-        finally:
-            bb.set_tuning(21, old_packed)
+        with tuning(bb, 25, 1), fused_alpha(bb):
+            # 32 < p <= 128 and the triangle mixture: unchanged, whatever the keys
+            rc, h, msg = create(bb.EngineConfig(n=200, p=40, true_alpha=0.0), 2, X)
+            assert rc == -1 and not h and "alpha" in msg, msg
+            rc, h, msg = create(bb.EngineConfig(n=80, p=12, true_alpha=0.0, method=4), 2, Xs)
+            assert rc == -1 and not h and "alpha" in msg, msg
+        with tuning(bb, 21, 1), fused_alpha(bb):
+            kept = fresh_batch(bb, Xs, y[:80], 2)
+            ref = fresh_batch(bb, Xs, y[:80], 2)
+            assert kept.threads() == 512 and kept.resident_per_cu() >= 1
+            tr_ref, st_ref = one_sweep(ref, 2)
         # the key is back at 0: a new batch is refused, the one created under it keeps its kernel
         assert bb.set_tuning(ALPHA_KEY, -1) == 0
         with pytest.raises(RuntimeError):

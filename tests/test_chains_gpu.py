@@ -14,6 +14,7 @@ import pytest
 
 from oracle import gibbs
 from tests.conftest import synthetic_problem
+from tests.tuning import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -160,8 +161,7 @@ def test_packed_instance_matches_oracle(gpu_lib):
     bb = gpu_lib
     X, y, _ = synthetic_problem(100, 20)
     K = 2 * torch.cuda.get_device_properties(0).multi_processor_count
-    old = bb.set_tuning(21, 1)
-    try:
+    with tuning(bb, 21, 1):
         b = bb.ChainBatch(bb.EngineConfig(n=100, p=20, seed=SEED), K, X, y)
         small = bb.ChainBatch(bb.EngineConfig(n=100, p=20, seed=SEED), K - 1, X, y)
         try:
@@ -171,8 +171,6 @@ def test_packed_instance_matches_oracle(gpu_lib):
             small.close()
         bb.set_seed(SEED)
         g = bb.bridge_reg_stb_chains(y, X, nsamp=300, nchains=K, burn=100)
-    finally:
-        bb.set_tuning(21, old)
     for c in (0, 1, K - 1):
         o = gibbs.bridge_regression_stable(y, X, 300, burn=100, alpha=0.5, seed=SEED, stream=c,
                                            method="chol")

@@ -23,7 +23,6 @@ see.
 
 Every test that sets a tuning key restores it in a finally.
 """
-import contextlib
 import math
 
 import numpy as np
@@ -32,6 +31,7 @@ import pytest
 from bayesbridge_amd.diagnostics import effective_size, rhat
 from tests import posterior_law as pl
 from tests.conftest import synthetic_problem
+from tests.tuning import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -39,17 +39,6 @@ SEED = 0x9051E4
 PACKED_KEY, WIDE_KEY, ALPHA_KEY = 21, 25, 26
 K_BATCH, M_BATCH = 256, 2000
 _traces = {}
-
-
-@contextlib.contextmanager
-def tuning(bb, **keys):
-    """bb_set_tuning keys for the duration, e.g. tuning(bb, k26=1)."""
-    old = {int(k[1:]): bb.set_tuning(int(k[1:]), v) for k, v in keys.items()}
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            bb.set_tuning(k, v)
 
 
 def assert_converged(beta, what):

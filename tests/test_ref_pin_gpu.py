@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 from tests.golden import make_ref_golden as mk
+from tests.tuning import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -54,15 +55,6 @@ def check(got, want, what=""):
     assert nf == 0, f"{what}: {nf} decision flips out of {len(want)} at " \
                     f"{np.flatnonzero(np.abs(got - want) > 1e-6 * np.abs(want))[:8]}"
     assert err < 1e-11, (what, err)
-
-
-@contextlib.contextmanager
-def tuning(bb, key, value):
-    old = bb.set_tuning(key, value)
-    try:
-        yield
-    finally:
-        bb.set_tuning(key, old)
 
 
 def design(n, p, seed=3):

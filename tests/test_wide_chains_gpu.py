@@ -7,7 +7,6 @@ bridge_reg_stable calls (np.array_equal on every returned array), and the batch 
 oracle within the whole-chain tolerances of tests/test_gpu_parity.py (elementwise 1e-6,
 posterior mean 1e-8).  Every test that sets the key restores it in a finally.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -18,6 +17,7 @@ from tests.conftest import synthetic_problem
 from tests.test_chains_gpu import (KEYS, assert_chain_equal, compare_chain, one_sweep,
                                    sequential)
 from tests.test_summary_gpu import assert_bitwise, check_against_trace_call, raw_of
+from tests.tuning import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +25,8 @@ SEED = 0xB4E5B41D6E
 WIDE_KEY = 25  # bb_set_tuning: wide fused chains (bb.set_wide_chains)
 
 
-@contextlib.contextmanager
 def wide_chains(bb, on=True):
-    old = bb.set_tuning(WIDE_KEY, 1 if on else 0)
-    try:
-        yield
-    finally:
-        bb.set_tuning(WIDE_KEY, old)
+    return tuning(bb, WIDE_KEY, 1 if on else 0)
 
 
 def ortho_wide_problem():

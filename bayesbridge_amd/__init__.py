@@ -26,7 +26,8 @@ __all__ = ["bridge_reg_stb", "bridge_reg", "retstable_ld", "set_seed", "get_rng_
            "set_rng_state", "Engine", "EngineConfig", "library", "device_count",
            "sample_lambda", "retstable_batch", "gram", "chol_solve", "bridge_reg_stb_chains",
            "bridge_reg_tri_chains", "ChainBatch", "compute_units",
-           "bridge_reg_stb_chains_summary", "bridge_reg_tri_chains_summary", "trace_summary"]
+           "bridge_reg_stb_chains_summary", "bridge_reg_tri_chains_summary", "trace_summary",
+           "bridge_reg_logit_chains", "bridge_reg_logit_chains_summary"]
 
 _lib: Optional[ctypes.CDLL] = None
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -76,7 +77,8 @@ EXPORTED_SYMBOLS = [
     "bb_chains_set_tri_state", "bb_chains_get_tri_basis", "bb_chains_threads",
     "bb_chains_set_threads", "bb_compute_units", "bridge_reg_stable_chains_summary",
     "bridge_regression_chains_summary", "bb_chains_summary_reset", "bb_chains_summary_add",
-    "bb_chains_summary_get", "bb_trace_summary",
+    "bb_chains_summary_get", "bb_trace_summary", "bridge_reg_logit_chains",
+    "bridge_reg_logit_chains_summary", "bb_chains_get_omega",
 ]
 
 
@@ -187,6 +189,10 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_engine_sparse_pairs.restype = c.c_longlong
     L.bridge_reg_logit.argtypes = [_dp] * 6 + [_dp] * 6 + [_ip] * 4 + [_dp]
     L.bb_engine_get_omega.argtypes = [c.c_void_p, _dp]
+    L.bridge_reg_logit_chains.argtypes = [_dp] * 6 + [_dp] * 6 + [_ip] * 4 + [_dp, _ip]
+    L.bridge_reg_logit_chains_summary.argtypes = ([_dp] * 5 + [_ip, _ip] + [_dp] * 2 + [_dp] * 6 +
+                                                  [_ip] * 4 + [_dp, _ip])
+    L.bb_chains_get_omega.argtypes = [c.c_void_p, c.c_int, _dp]
     L.bb_pg_batch.argtypes = [_dp, _dp, c.c_int, c.c_uint64, c.c_uint64, c.c_uint64]
     L.bb_engine_sparse_info.argtypes = [c.c_void_p, c.POINTER(c.c_longlong),
                                         c.POINTER(c.c_longlong), _ip, _ip]
@@ -764,6 +770,80 @@ def bridge_reg_logit(y, X, nsamp, alpha=0.5, nu_shape=2.0, nu_rate=2.0, alpha_a=
                        i(M), i(burn), ctypes.byref(rt))
     return {"beta": beta.T.copy(), "lambda": lam.T.copy(), "tau": tau, "alpha": alph,
             "runtime": rt.value}
+
+
+def _logit_chains_args(entry, y, X, nsamp, nchains, nu_shape, nu_rate, alpha_a, alpha_b):
+    """The checked inputs of the logistic chains calls: y, X (Fortran order), P, N, M, K."""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    N = y.shape[0]
+    R, P = X.shape
+    M, K = int(nsamp), int(nchains)
+    if not check_parameters(N, R, M, 0.0, 0.0, nu_shape, nu_rate, alpha_a,
+                            alpha_b) or not _is_above(K, 1, "nchains"):
+        raise ValueError(f"{entry}: invalid parameters")
+    if not np.all((y == 0) | (y == 1)):
+        raise ValueError(f"{entry}: y must be 0/1")
+    return y, np.asfortranarray(X), P, N, M, K
+
+
+def bridge_reg_logit_chains(y, X, nsamp, nchains, alpha=0.5, nu_shape=2.0, nu_rate=2.0,
+                            alpha_a=1.0, alpha_b=1.0, tau_true=0.0, burn=500):
+    """``nchains`` independent logistic-bridge chains in one call, through
+    ``.C("bridge_reg_logit_chains", ...)``: chain c draws under the key of the c-th of
+    ``nchains`` consecutive ``bridge_reg_logit`` calls.  Small designs (P <= 32, P <= N,
+    N <= 4096; alpha known or, with ``alpha <= 0``, sampled) run every chain side by side, a
+    workgroup per chain with X'Omega X formed inside it every sweep; chain c then agrees with
+    that call up to the summation order of X'Omega X and does not depend on ``nchains``.  Other
+    designs run their chains one after another and return exactly what those calls return.
+
+    Returns a dict: beta, lambda (K x M x P), tau, alpha (K x M), runtime (one number for the
+    batch).
+    """
+    L = library()
+    _require_gpu()
+    y, Xf, P, N, M, K = _logit_chains_args("bridge_reg_logit_chains", y, X, nsamp, nchains,
+                                           nu_shape, nu_rate, alpha_a, alpha_b)
+    # P x M x K column-major is (K, M, P) in C order
+    beta, lam = np.zeros((K, M, P)), np.zeros((K, M, P))
+    tau, alph = np.zeros((K, M)), np.zeros((K, M))
+    d = lambda v: ctypes.byref(ctypes.c_double(float(v)))  # noqa: E731
+    i = lambda v: ctypes.byref(ctypes.c_int(int(v)))  # noqa: E731
+    rt = ctypes.c_double(0.0)
+    L.bridge_reg_logit_chains(_p(beta), _p(lam), _p(tau), _p(alph), _p(y), _p(Xf), d(nu_shape),
+                              d(nu_rate), d(alpha_a), d(alpha_b), d(tau_true), d(alpha), i(P),
+                              i(N), i(M), i(burn), ctypes.byref(rt), i(K))
+    return {"beta": beta, "lambda": lam, "tau": tau, "alpha": alph, "runtime": rt.value}
+
+
+def bridge_reg_logit_chains_summary(y, X, nsamp, nchains, alpha=0.5, nu_shape=2.0, nu_rate=2.0,
+                                    alpha_a=1.0, alpha_b=1.0, tau_true=0.0, burn=500,
+                                    maxlag=None):
+    """``bridge_reg_logit_chains`` returning posterior summaries instead of traces, through
+    ``.C("bridge_reg_logit_chains_summary", ...)``; the sig2 column is the constant 1.  See
+    ``bridge_reg_stb_chains_summary`` for what is returned."""
+    entry = "bridge_reg_logit_chains_summary"
+    L = library()
+    _require_gpu()
+    y, Xf, P, N, M, K = _logit_chains_args(entry, y, X, nsamp, nchains, nu_shape, nu_rate,
+                                           alpha_a, alpha_b)
+    lag = _summary_maxlag(M, maxlag)
+    if not 0 <= lag <= SUMMARY_MAX_LAG:
+        raise ValueError(f"{entry}: maxlag must be in [0, {SUMMARY_MAX_LAG}] (got {lag})")
+    raw = _summary_buffers(K, P + 3, lag)
+    d = lambda v: ctypes.byref(ctypes.c_double(float(v)))  # noqa: E731
+    i = lambda v: ctypes.byref(ctypes.c_int(int(v)))  # noqa: E731
+    rt = ctypes.c_double(0.0)
+    L.bridge_reg_logit_chains_summary(
+        _p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]), _p(raw["hmean"]), _p(raw["hvar"]),
+        raw["flags"].ctypes.data_as(_ip), i(lag), _p(y), _p(Xf), d(nu_shape), d(nu_rate),
+        d(alpha_a), d(alpha_b), d(tau_true), d(alpha), i(P), i(N), i(M), i(burn),
+        ctypes.byref(rt), i(K))
+    if np.isnan(raw["mean"]).all() and rt.value == 0.0:
+        raise RuntimeError(f"{entry}: the call returned no summaries: {_err()}")
+    return _summary_result(raw, P, M, lag, rt.value)
 
 
 def pg_batch(psi, seed, stream=0, t=0):
@@ -1442,7 +1522,9 @@ class ChainBatch:
     shape through tri_trace / set_tri_state).  A stable-mixture batch needs P <= 32, or
     P <= 128 when created after ``set_wide_chains(True)`` (it then keeps the wide kernel); with
     cfg.true_alpha <= 0 it needs P <= 32 and ``set_fused_alpha(True)`` at creation, and each
-    chain then samples its alpha inside the launch (``run``'s mcmc_phase selects the prior)."""
+    chain then samples its alpha inside the launch (``run``'s mcmc_phase selects the prior).
+    cfg.method = 6 makes it a logistic-bridge batch (P <= 32, P <= N, N <= 4096; alpha known or
+    sampled, no tuning key; y in {0, 1}); ``omega(chain)`` is a chain's last Polya-Gamma draw."""
 
     def __init__(self, cfg: EngineConfig, nchains: int, X, y):
         L = library()
@@ -1497,6 +1579,12 @@ class ChainBatch:
         beta = np.ascontiguousarray(beta, dtype=np.float64)
         _check(library().bb_chains_set_state(self._h, int(chain), _p(beta), tau, sig2, alpha),
                "bb_chains_set_state")
+
+    def omega(self, chain: int):
+        """Logistic bridge: the Polya-Gamma omega (n values) of the chain's last sweep."""
+        om = np.zeros(self._c.n)
+        _check(library().bb_chains_get_omega(self._h, int(chain), _p(om)), "bb_chains_get_omega")
+        return om
 
     def tri_trace(self, chain: int, slot0: int, count: int):
         """Triangle method: u and shape traces of one chain (omega is ``trace()['lambda']``)."""

@@ -1662,9 +1662,16 @@ const char *chains_refusal(const bb_config &c) {
         if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
         return nullptr;
     }
+    if (c.method == LOGIT) {  // the logistic bridge: bb_logit_chain.hip, alpha known or sampled
+        static_assert(kSmallChainMaxP == 32 && kLogitChainMaxN == 4096, "the messages say so");
+        if (c.p > kSmallChainMaxP) return "a logistic chain batch needs p <= 32";
+        if (c.p > c.n) return "a logistic chain batch needs p <= n";
+        if (c.n > kLogitChainMaxN) return "a logistic chain batch needs n <= 4096";
+        return nullptr;
+    }
     if (c.method != AUTO && c.method != CHOL)
         return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or "
-               "1) or the triangle mixture (method 4)";
+               "1), the triangle mixture (method 4) or the logistic bridge (method 6)";
     if (g_chains_wide) {  // bb_set_tuning key 25: bb_wide.hip's kernel above 32
         static_assert(kWideChainMaxP == 128, "the message below says 128");
         if (c.p > kWideChainMaxP) return "a chain batch needs p <= 128 (wide fused chains on)";
@@ -1682,7 +1689,8 @@ const char *chains_refusal(const bb_config &c) {
 
 // ---------------------------------------------------------------------------
 // Chain batch: K chains of one small design, a workgroup each (bb_small.hip k_small_chains;
-// the triangle mixture: bb_tri.hip k_tri_chains, with omega in lam).
+// the triangle mixture: bb_tri.hip k_tri_chains, with omega in lam; the logistic bridge:
+// bb_logit_chain.hip k_logit_chains, with each chain's last Polya-Gamma omega in `omega`).
 // One engine (`proto`, never run) holds what the chains share -- X, y, X'X, X'y, the
 // triangle mixture's SVD basis and the least-squares start -- and makes each chain's pre-burn
 // draw under that chain's key; the state, the error word and the trace rings are per chain
@@ -1699,9 +1707,11 @@ struct bb_chains {
            *tr_alpha = nullptr;
     // triangle mixture (proto->tri()): u and shape beside omega (lam)
     double *u = nullptr, *shape = nullptr, *tr_u = nullptr, *tr_shape = nullptr;
+    double *omega = nullptr;  // logistic bridge: [chain][n], the omega of the last sweep
     Throttle ahead;
 
     bool tri() const { return proto->tri(); }
+    bool logit() const { return proto->logit(); }
     ~bb_chains() {
         if (proto && proto->stream) (void)hipStreamSynchronize(proto->stream);
         for (void *q : owned) (void)hipFree(q);
@@ -1757,7 +1767,10 @@ struct bb_chains {
                              .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
         const ChainRun r =
             e->chain_run(base_stream, t0, count, first_slot, slot_step, cap, mcmc_phase);
-        if (wide) {
+        if (logit()) {
+            if (launch_logit_chains(e->stream, K, e->chain_design(), st, tr, r, omega) != 0)
+                throw HipError("no logistic chain-batch instance for this design");
+        } else if (wide) {
             if (launch_wide_chains(e->stream, K, e->chain_design(), st, tr, r) != 0)
                 throw HipError("no wide chain-batch instance for this p");
         } else if (!tri())
@@ -2286,7 +2299,10 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
         c.p_local = c.p;
         c.trace_capacity = 1;  // the shared engine records its own slot 0 only
         if (bb_engine_create(&c, X, y, &b->proto) != 0) throw HipError(g_last_error);
-        if (!b->proto->fused || b->proto->tri() != (c.method == TRI))
+        // (the logistic prototype is a general-path engine: its batch kernel has no single-chain
+        // twin, so there is no bb_engine::fused to ask for)
+        if (b->proto->logit() != (c.method == LOGIT) ||
+            (!b->proto->logit() && (!b->proto->fused || b->proto->tri() != (c.method == TRI))))
             throw HipError("this design does not run as a fused small chain");
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
@@ -2315,6 +2331,10 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
             b->tr_u = dalloc<double>(K * cap * p, o);
             b->tr_shape = dalloc<double>(K * cap * p, o);
         }
+        if (b->logit()) {
+            b->omega = dalloc<double>(K * (size_t)c.n, o);
+            HIPCHECK(hipMemset(b->omega, 0, K * (size_t)c.n * sizeof(double)));
+        }
     } catch (std::exception &ex) {
         const std::string msg = ex.what();
         delete b;
@@ -2331,6 +2351,8 @@ int bb_chains_count(const bb_chains *b) { return b->K; }
 int bb_chains_resident_per_cu(const bb_chains *b) {
     if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
     if (b->tri()) return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads);
+    if (b->logit())
+        return logit_chains_resident_per_cu(b->proto->n, b->p, !b->proto->hy.know_alpha);
     if (b->wide) return wide_chains_resident_per_cu(b->p);
     return small_chains_resident_per_cu(b->proto->n, b->p, b->packed, !b->proto->hy.know_alpha);
 }
@@ -2406,6 +2428,17 @@ int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau,
         HIPCHECK(hipMemcpy(b->beta + chain * pl, beta, pl * sizeof(double),
                            hipMemcpyHostToDevice));
         scalars_write(b->sc + chain, tau, sig2, alpha);
+    });
+}
+
+int bb_chains_get_omega(bb_chains *b, int chain, double *omega) {
+    return guarded([&] {
+        b->check_chain(chain);
+        if (!b->logit()) throw HipError("not a logistic chain batch");
+        HIPCHECK(hipStreamSynchronize(b->stream()));
+        const size_t n = (size_t)b->proto->n;
+        HIPCHECK(hipMemcpy(omega, b->omega + chain * n, n * sizeof(double),
+                           hipMemcpyDeviceToHost));
     });
 }
 
@@ -3335,6 +3368,37 @@ Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, Trace
         b, out, runtime);
 }
 
+// the logistic family: the stable driver's schedule under its own banner
+CallKind logit_kind(int b) {
+    return stable_kind(b, "Bridge Regression (logistic, Polya-Gamma mix. of normals):");
+}
+
+// a logistic entry's y, checked before a key is taken or an output is touched
+bool logit_y_ok(const char *entry, const double *yp, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!(yp[i] == 0.0 || yp[i] == 1.0)) {
+            set_error("%s: logistic bridge needs y in {0, 1} (y[%d] = %g)", entry, i, yp[i]);
+            printf("Error: %s\n", g_last_error.c_str());
+            fflush(stdout);
+            return false;
+        }
+    return true;
+}
+
+// bb_config of a .C bridge_reg_logit_chains call: bridge_reg_logit's (sig2 == 1, no prior on
+// it) with the logistic method and K keys taken
+bb_config logit_chains_config(const double *nu_shape, const double *nu_rate,
+                              const double *alpha_a, const double *alpha_b,
+                              const double *true_tau, const double *true_alpha, int p, int n,
+                              int m, int nchains) {
+    const double zero = 0.0, one = 1.0;
+    const int no = 0;
+    bb_config c = stable_call_config(&zero, &zero, nu_shape, nu_rate, alpha_a, alpha_b, &one,
+                                     true_tau, true_alpha, p, n, m, &no, nchains);
+    c.method = LOGIT;
+    return c;
+}
+
 // a chains entry's nchains, checked before a key is taken or an output is touched
 bool nchains_ok(const char *entry, int nchains) {
     if (nchains >= 1) return true;
@@ -3561,6 +3625,43 @@ void bridge_reg_logit(double *betap, double *lambdap, double *taup, double *alph
                                            &one, true_tau, true_alpha, *P, *N, *M, &no);
     if (logit_call(c, yp, Xp, *burn, {betap, lambdap, nullptr, taup, alphap}, runtime) ==
         OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
+void bridge_reg_logit_chains(double *betap, double *lambdap, double *taup, double *alphap,
+                             const double *yp, const double *Xp, const double *nu_shape,
+                             const double *nu_rate, const double *alpha_a,
+                             const double *alpha_b, const double *true_tau,
+                             const double *true_alpha, const int *P, const int *N, const int *M,
+                             const int *burn, double *runtime, const int *nchains) {
+    const char *entry = "bridge_reg_logit_chains";
+    if (!nchains_ok(entry, *nchains) || !logit_y_ok(entry, yp, *N)) return;
+    const bb_config c = logit_chains_config(nu_shape, nu_rate, alpha_a, alpha_b, true_tau,
+                                            true_alpha, *P, *N, *M, *nchains);
+    // the sig2 trace (the constant 1) has no output: it lands in a buffer of the call's own
+    std::vector<double> sig2((size_t)c.trace_capacity * (size_t)*nchains);
+    if (chains_call(logit_kind(*burn), c, *nchains, yp, Xp, *burn,
+                    {betap, lambdap, sig2.data(), taup, alphap}, runtime) == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
+void bridge_reg_logit_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
+                                     double *hvarp, int *flagsp, const int *maxlag,
+                                     const double *yp, const double *Xp, const double *nu_shape,
+                                     const double *nu_rate, const double *alpha_a,
+                                     const double *alpha_b, const double *true_tau,
+                                     const double *true_alpha, const int *P, const int *N,
+                                     const int *M, const int *burn, double *runtime,
+                                     const int *nchains) {
+    const char *entry = "bridge_reg_logit_chains_summary";
+    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag) ||
+        !logit_y_ok(entry, yp, *N))
+        return;
+    const bb_config c = logit_chains_config(nu_shape, nu_rate, alpha_a, alpha_b, true_tau,
+                                            true_alpha, *P, *N, *M, *nchains);
+    if (chains_summary_call(entry, logit_kind(*burn), c, *nchains, yp, Xp, *burn,
+                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag},
+                            runtime) == OUT_INTERRUPTED)
         reraise_interrupt();
 }
 

@@ -481,6 +481,20 @@ void launch_small_chains(hipStream_t s, int nchains, int packed, const ChainDesi
                          const ChainState &c, const ChainTraces &tr, const ChainRun &r);
 int small_chains_resident_per_cu(int n, int p, int packed, int mh);
 
+// Whole logistic-bridge sweeps (Polya-Gamma latents, sig2 == 1) of `nchains` independent chains
+// in one launch, a workgroup per chain (bb_logit_chain.hip k_logit_chains): psi = X beta and
+// S_alpha, tau, lambda, omega ~ PG(1, psi), A = X' Omega X + diag(lambda / tau^2) formed in the
+// workgroup every sweep, beta by its Cholesky draw, and alpha's MH step where d.hy.know_alpha
+// == 0.  For p <= kSmallChainMaxP, p <= n <= kLogitChainMaxN (omega stays in LDS); d.cvec =
+// X'(y - 1/2), d.G and d.y are not read.  omega (nchains x n) receives every chain's omega of the
+// last sweep.  Returns -1 (nothing launched) outside those shapes.
+// logit_chains_resident_per_cu: the workgroups the runtime keeps resident on one CU for an
+// n x p design (-1 if the query fails or the shape is outside).
+constexpr int kLogitChainMaxN = 4096;
+int launch_logit_chains(hipStream_t s, int nchains, const ChainDesign &d, const ChainState &c,
+                        const ChainTraces &tr, const ChainRun &r, double *omega);
+int logit_chains_resident_per_cu(int n, int p, int mh);
+
 // The same fused stable sweeps for kSmallChainMaxP < p <= kWideChainMaxP (bb_wide.hip; opt-in,
 // bb_set_tuning key 25): X and G are read from memory, U alone is in LDS.  The single chain
 // (k_wide_chain) and the batch (k_wide_chains, a workgroup per chain) run one sweep body, 256

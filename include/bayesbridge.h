@@ -299,6 +299,17 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
  * bb_chains_set_threads picks another instance of a triangle batch for A/B measurement (512,
  * 256 or 128; -1 if there is none) -- never a change of results.
  *
+ * The logistic bridge (cfg->method == 6; bb_logit_chain.hip k_logit_chains) runs as a batch for
+ * p <= 32, p <= n, n <= 4096, world == 1, alpha known or unknown (no tuning key): each
+ * workgroup runs its chain's whole sweeps -- psi = X beta, tau, lambda, omega ~ PG(1, psi),
+ * A = X'Omega X + diag(lambda / tau^2) summed over the rows in a fixed order, the Cholesky
+ * draw of beta and, where alpha is unknown, its MH step under the (alpha_a, alpha_b) prior in
+ * both phases -- on the counters of the general logistic path.  A single bb_engine of method 6
+ * keeps the general path, so chain c agrees with the engine of its key up to the summation
+ * order of X'Omega X (not bit for bit); it does not depend on nchains.  y must be in {0, 1}
+ * (the .C entries check it).  bb_chains_get_omega returns chain `chain`'s omega of its last
+ * sweep (n values), as bb_engine_get_omega does for an engine; sig2 is the constant 1.
+ *
  * init_state, run, sync, get_trace, get_state and set_state mean for chain `chain` what the
  * bb_engine_* calls mean for a single engine; bb_chains_run advances every chain by `count`
  * sweeps.  bb_chains_error_flags returns chain `chain`'s flag word (a failed Cholesky pivot
@@ -329,6 +340,7 @@ int bb_chains_get_tri_trace(bb_chains *b, int chain, int slot0, int count, doubl
                             double *shape);
 int bb_chains_set_tri_state(bb_chains *b, int chain, const double *u);
 int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d);
+int bb_chains_get_omega(bb_chains *b, int chain, double *omega);
 int bb_chains_threads(const bb_chains *b);
 int bb_chains_set_threads(bb_chains *b, int threads);
 
@@ -377,6 +389,25 @@ void bridge_regression_chains(double *betap, double *up, double *omegap, double 
                               const int *N, const int *M, const int *burn, double *runtime,
                               const int *ortho, const int *betaburn, const int *use_hmc,
                               const int *nchains);
+
+/*
+ * K independent chains of bridge_reg_logit in one call: its 17 arguments with `nchains`
+ * appended.  betap and lambdap are P x M x K column-major, taup and alphap are M x K; runtime
+ * is one number for the batch.  One call key is taken and chain c draws under (k0, k1 + c)
+ * (outside R the stream counter advances by K), on bridge_reg_logit's schedule.  Designs a
+ * logistic chain batch accepts (bb_chains_create: p <= 32, p <= n, n <= 4096; alpha known or
+ * unknown) run as one batch, a workgroup per chain, and chain c then agrees with the c-th of K
+ * consecutive bridge_reg_logit calls up to the summation order of X'Omega X; every other
+ * design bridge_reg_logit accepts runs its K chains one after another and returns exactly what
+ * those calls return.  nchains < 1 or a y outside {0, 1} prints an error (bb_last_error) and
+ * returns before a key is taken or an output is written.
+ */
+void bridge_reg_logit_chains(double *betap, double *lambdap, double *taup, double *alphap,
+                             const double *yp, const double *Xp, const double *nu_shape,
+                             const double *nu_rate, const double *alpha_a,
+                             const double *alpha_b, const double *true_tau,
+                             const double *true_alpha, const int *P, const int *N, const int *M,
+                             const int *burn, double *runtime, const int *nchains);
 
 /*
  * Posterior summaries of a chain batch without copying its traces.  The parameters of a chain
@@ -429,6 +460,16 @@ void bridge_reg_stable_chains_summary(double *meanp, double *varp, double *acovp
                                       const double *true_alpha, const int *P, const int *N,
                                       const int *M, const int *burn, double *runtime,
                                       const int *ortho, const int *nchains);
+/* ... of bridge_reg_logit_chains (Q = P + 3 with the sig2 column the constant 1; a y outside
+ * {0, 1} is refused like nchains < 1) */
+void bridge_reg_logit_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
+                                     double *hvarp, int *flagsp, const int *maxlag,
+                                     const double *yp, const double *Xp, const double *nu_shape,
+                                     const double *nu_rate, const double *alpha_a,
+                                     const double *alpha_b, const double *true_tau,
+                                     const double *true_alpha, const int *P, const int *N,
+                                     const int *M, const int *burn, double *runtime,
+                                     const int *nchains);
 /* ... and of bridge_regression_chains (the triangle mixture) */
 void bridge_regression_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
                                       double *hvarp, int *flagsp, const int *maxlag,

@@ -38,6 +38,16 @@ single call with the key on (k_wide_chain), and batches at K = 8, CUs and 2 CUs 
 kernel-only rate and the resident workgroups per CU.  Default 1000 samples after a burn-in of
 200 (the traces of 2 CUs chains of 5000 samples would be 4 GB).
 
+--logit measures the logistic chain batch (bridge_reg_logit_chains, bb_logit_chain.hip
+k_logit_chains) at lg5 (the 200 x 5 design of the logistic posterior-law tests) and lg32
+(1000 x 32, the same generator) into profiles/chains_logit_{lg5,lg32}.json: alternated within
+each round, the single bridge_reg_logit call (the general path) and batches at K = 1, CUs and
+4 CUs, each as the call, kernel only and as the summary call, with the resident workgroups per
+CU, and one CPU core running the compiled oracle chain (oracle.cpu_logit_chain).  The baseline a
+batch has to beat is K sequential general-path chains: --logit --mode single [--tree DIR]
+measures the single call (on the parent checkout, say) as one JSON line, which --baseline FILE
+merges.  Default 1000 samples after a burn-in of 200.
+
 Protocol: one warm-up call, then REPS rounds, each round visiting every K (and the
 single-chain bridge_reg_stb call) once, so slow drifts of the device hit every K alike; the
 median over rounds is reported with the min and max beside it.
@@ -50,6 +60,8 @@ median over rounds is reported with the min and max beside it.
   python tools/bench_chains.py --wide [--designs dbi]
   python tools/bench_chains.py --alpha --mode single --tree DIR --nsamp 100 --burn 50 > FILE
   python tools/bench_chains.py --alpha --baseline FILE
+  python tools/bench_chains.py --logit --mode single --tree DIR > FILE
+  python tools/bench_chains.py --logit --baseline FILE
 """
 import argparse
 import json
@@ -85,6 +97,22 @@ def designs():
         y = X @ b + 2.0 * rng.standard_normal(n)
         out[name] = (np.asfortranarray(X), y - y.mean())
     return out
+
+
+def logit_problem(n, p, seed, scale=1.0):
+    """The generator of the logistic tests (tests/test_logit_gpu.py), copied: tools do not
+    import tests."""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, p)) * scale
+    b = np.zeros(p)
+    k = max(3, p // 20)
+    b[:k] = rng.uniform(0.5, 1.5, k) * rng.choice([-1.0, 1.0], k)
+    y = (rng.random(n) < 1.0 / (1.0 + np.exp(-X @ b))).astype(np.float64)
+    return np.asfortranarray(X), y
+
+
+def logit_designs():
+    return {"lg5": logit_problem(200, 5, seed=3), "lg32": logit_problem(1000, 32, seed=3)}
 
 
 class Method:
@@ -441,11 +469,117 @@ def bench_alpha_fallback(me, args):
                       "fallback_chains_sweeps_per_s": out}), flush=True)
 
 
+def logit_kernel_rate(bb, X, y, K, nsamp):
+    """kernel_rate for the logistic batch (method 6)."""
+    n, p = X.shape
+    b = bb.ChainBatch(bb.EngineConfig(n=n, p=p, seed=SEED, method=6), K, X, y)
+    try:
+        b.init_state()
+        b.run(1, 200, 0, 0, 0)
+        b.sync()
+        t0 = time.perf_counter()
+        for s in range(0, nsamp, 50):
+            b.run(201 + s, min(50, nsamp - s), -1, 1, 1)
+        b.sync()
+        return K * nsamp / (time.perf_counter() - t0), b.resident_per_cu()
+    finally:
+        b.close()
+
+
+def bench_logit(bb, name, X, y, cus, args):
+    """The logistic batch against the single general-path call, alternated within each round."""
+    sys.path.insert(0, ROOT)
+    import oracle
+
+    Ks = [k for k in (args.chains or dict.fromkeys([1, cus, 4 * cus])) if k <= args.max_chains]
+    nsamp, burn = args.nsamp, args.burn
+    bb.set_seed(SEED)
+    bb.bridge_reg_logit(y, X, nsamp=100, burn=50)  # warm-up
+    bb.bridge_reg_logit_chains(y, X, nsamp=100, nchains=2, burn=50)
+    bb.bridge_reg_logit_chains_summary(y, X, nsamp=100, nchains=2, burn=50)
+    keys = ("call", "kernel", "summary")
+    v = {K: {k: [] for k in keys} for K in Ks}
+    single, cpu, res = [], [], {}
+    for _ in range(args.reps):
+        bb.set_seed(SEED)
+        single.append(nsamp / bb.bridge_reg_logit(y, X, nsamp=nsamp, burn=burn)["runtime"])
+        t0 = time.perf_counter()
+        oracle.cpu_logit_chain(y, X, nsamp, burn=burn, seed=SEED, stream=0)
+        cpu.append((nsamp + burn) / (time.perf_counter() - t0))
+        for K in Ks:
+            bb.set_seed(SEED)
+            out = bb.bridge_reg_logit_chains(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            v[K]["call"].append(K * nsamp / out["runtime"])
+            del out
+            kr, res[K] = logit_kernel_rate(bb, X, y, K, nsamp)
+            v[K]["kernel"].append(kr)
+            bb.set_seed(SEED)
+            out = bb.bridge_reg_logit_chains_summary(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            v[K]["summary"].append(K * nsamp / out["runtime"])
+    base, base_meta = None, None
+    if args.baseline:
+        with open(args.baseline) as f:
+            for line in f:
+                if line.startswith("{"):
+                    r = json.loads(line)
+                    base = r.get("single_call_sweeps_per_s", {}).get(name, base)
+                    base_meta = {k: r.get(k) for k in ("source_sha", "nsamp", "burn", "reps")}
+    s1, c1 = spread(single), spread(cpu)
+    rows = []
+    for K in Ks:
+        s = {k: spread(v[K][k]) for k in keys}
+        row = {"chains": K, "resident_per_cu": res[K], "call_sweeps_per_s": s["call"],
+               "kernel_sweeps_per_s": s["kernel"], "summary_call_sweeps_per_s": s["summary"],
+               # K sequential single calls run at the single call's rate in aggregate
+               "vs_sequential_this_tree": s["call"]["median"] / s1["median"],
+               "cpu_cores_worth": s["call"]["median"] / c1["median"]}
+        if base:
+            row["vs_sequential_parent"] = s["call"]["median"] / base["median"]
+            row["beats_sequential_parent_beyond_spread"] = s["call"]["min"] > base["max"]
+        rows.append(row)
+    from bayesbridge_amd import _kernel_code
+
+    p = X.shape[1]
+    lanes = "512, 64, 16" if p <= 8 else "512, 32, 8" if p <= 16 else "512, 16, 8"
+    kname = f"bb::k_logit_chains<{lanes}, false>"
+    rec = {"design": name, "n": int(X.shape[0]), "p": int(p), "nsamp": nsamp, "burn": burn,
+           "reps": args.reps, "compute_units": cus, "single_call_sweeps_per_s": s1,
+           "cpu_core_oracle_sweeps_per_s": c1, "chains": rows,
+           "kernels": {kname: {"code_sha": _kernel_code.code_sha(kname)}}}
+    if base:
+        rec["parent_single_call_sweeps_per_s"] = base
+        rec["parent_measured_with"] = base_meta
+    return rec
+
+
+def bench_logit_single(bb, args):
+    """bridge_reg_logit alone at the logistic designs (one JSON line): the baseline of --logit,
+    through --baseline."""
+    out = {}
+    for name, (X, y) in logit_designs().items():
+        if name not in args.designs.split(","):
+            continue
+        bb.set_seed(SEED)
+        bb.bridge_reg_logit(y, X, nsamp=100, burn=50)
+        v = []
+        for _ in range(args.reps):
+            bb.set_seed(SEED)
+            v.append(args.nsamp / bb.bridge_reg_logit(y, X, nsamp=args.nsamp,
+                                                      burn=args.burn)["runtime"])
+        out[name] = spread(v)
+        print(f"{name} single call {out[name]}", file=sys.stderr, flush=True)
+    print(json.dumps({"tree": args.tree, "source_sha": bb._build.source_sha(),
+                      "nsamp": args.nsamp, "burn": args.burn, "reps": args.reps,
+                      "single_call_sweeps_per_s": out}), flush=True)
+
+
 def bench_single(me, args):
     """The single-chain call alone at both designs (one JSON line): the A/B against another
     checkout."""
     if args.alpha:
         return bench_alpha_fallback(me, args)
+    if args.logit:
+        return bench_logit_single(me.bb, args)
     out = {}
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
@@ -481,16 +615,19 @@ def main():
                     help="the wide fused chains (key 25) at dbi / bhi (profiles/chains_wide_*)")
     ap.add_argument("--alpha", action="store_true",
                     help="alpha unknown under key 26 (profiles/chains_alpha_*)")
+    ap.add_argument("--logit", action="store_true",
+                    help="the logistic chain batch at lg5 / lg32 (profiles/chains_logit_*)")
     ap.add_argument("--baseline", default=None,
-                    help="--alpha: the JSON line of an --alpha --mode single run to merge")
+                    help="--alpha / --logit: the JSON line of a --mode single run to merge")
     ap.add_argument("--chains", type=lambda v: [int(t) for t in v.split(",")], default=None,
                     help="--summary: the batch sizes (default CUs,4 CUs); --alpha: 1,256,1024")
     ap.add_argument("--tag", default="", help="suffix of the output files' names")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
-    args.designs = args.designs or ("dbi,bhi" if args.wide else "c1,db")
-    args.nsamp = args.nsamp or (1000 if args.wide else 5000)
-    args.burn = args.burn if args.burn is not None else (200 if args.wide else 500)
+    args.designs = args.designs or ("dbi,bhi" if args.wide else "lg5,lg32" if args.logit
+                                    else "c1,db")
+    args.nsamp = args.nsamp or (1000 if args.wide or args.logit else 5000)
+    args.burn = args.burn if args.burn is not None else (200 if args.wide or args.logit else 500)
     sys.path.insert(0, os.path.abspath(args.tree))
     import torch
 
@@ -505,8 +642,27 @@ def main():
         return bench_single(me, args)
     cus = (bb.compute_units() if hasattr(bb, "compute_units")
            else int(torch.cuda.get_device_properties(0).multi_processor_count))
-    for name, (X, y) in designs().items():
+    for name, (X, y) in (logit_designs() if args.logit else designs()).items():
         if name not in args.designs.split(","):
+            continue
+        if args.logit:
+            rec = bench_logit(bb, name, X, y, cus, args)
+            rec["source_sha"] = bb._build.source_sha()
+            with open(os.path.join(args.out_dir, f"chains_logit_{name}{args.tag}.json"), "w") as f:
+                json.dump(rec, f, indent=1)
+                f.write("\n")
+            s1, c1 = rec["single_call_sweeps_per_s"], rec["cpu_core_oracle_sweeps_per_s"]
+            print(f"{name} single call {s1['median']:.0f} sweeps/s [{s1['min']:.0f}, "
+                  f"{s1['max']:.0f}]  one CPU core {c1['median']:.0f}", flush=True)
+            for r in rec["chains"]:
+                a, k, sm = (r["call_sweeps_per_s"], r["kernel_sweeps_per_s"],
+                            r["summary_call_sweeps_per_s"])
+                print(f"{name} K={r['chains']:5d} call {a['median']:.0f} sweeps/s "
+                      f"[{a['min']:.0f}, {a['max']:.0f}]  kernel {k['median']:.0f}  summary "
+                      f"{sm['median']:.0f}  x{r['vs_sequential_this_tree']:.0f} sequential"
+                      + (f" (x{r['vs_sequential_parent']:.0f} parent)"
+                         if "vs_sequential_parent" in r else "")
+                      + f"  resident/CU {r['resident_per_cu']}", flush=True)
             continue
         if args.alpha:
             rec = bench_alpha(me, name, X, y, cus, args)

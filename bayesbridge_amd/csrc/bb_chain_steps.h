@@ -1,4 +1,4 @@
-// bb_chain_steps.h -- the steps every fused chain sweep opens with, written once (gfx950).
+// bb_chain_steps.h -- the steps the fused chain sweeps share, written once (gfx950).
 //
 // small_chain_body (bb_small_body.h), wide_chain_body (bb_wide.hip) and tri_chain_body
 // (bb_tri.hip) run one chain in one workgroup, in the reference's order
@@ -7,10 +7,18 @@
 //   chain_scalars     tau | beta and sig2 | beta      BridgeRegression.cpp:453-465, :436-450
 //   chain_lambda      lambda | beta, tau              :506-510 (stable mixture: small, wide)
 //   chain_beta_ortho  beta | rest, orthogonal design  :514-521 (small, wide)
+// small_chain_body and k_logit_chains (bb_logit_chain.hip) factor a system of p <= kSmallMaxP
+// entry by entry and end their sweeps with the same steps:
+//   chain_tri_owners  the upper-triangle entries a thread owns
+//   chain_factor      A = U'U, right-looking            :560
+//   chain_solves      U'v = c, U m = v, U x = z in wave 0
+//   chain_alpha_step  alpha | beta, tau in wave 0 (the instances that sample alpha)
 // The bodies keep what differs: the staging of X and G, the look-ahead of counter-only
-// variates, the factorisations and solves, the triangle's wave-0 update and the alpha step.
-// All are force-inlined into the caller's sweep loop and hold no barrier: the barriers between
-// the steps stay in the body, where the LDS they order is declared.
+// variates, how A is formed, the wide and triangle factorisations and solves, the triangle's
+// wave-0 update.
+// All are force-inlined into the caller's sweep loop and hold no LDS declaration; but for
+// chain_factor's two barriers per pivot they hold no barrier either: the barriers between the
+// steps stay in the body, where the LDS they order is declared.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -128,6 +136,138 @@ __device__ __forceinline__ void chain_beta_ortho(int p, double *sb, const double
         const double sd = sqrt(sig2 / uu);
         const double m = c[tid] / uu;
         sb[tid] = m + sd * z[tid];
+    }
+}
+
+namespace {
+
+constexpr int kSmallMaxP = kSmallChainMaxP;
+
+// alpha_mh_accept (bb_sampler.h) out of line: one thread's scalar work, whose registers are
+// then not the sweep loop's (inlined, the MH instances spill 122-125 VGPRs and take 504-520 B
+// of scratch per lane; so, 5-8 and 40-56).  Internal linkage: a code object that does not call
+// it does not hold it, and keeps its kernels' identity (bayesbridge_amd/_kernel_code.py).
+[[maybe_unused]] __device__ __noinline__ double alpha_mh_decide(double a_old, double a_new, double d_new,
+                                               double Sn, double So, double pp, double pr_a,
+                                               double pr_b, double lbc, double u1) {
+    return alpha_mh_accept(a_old, a_new, d_new, Sn, So, pp, pr_a, pr_b, lbc, u1);
+}
+
+}  // namespace
+
+// Upper-triangle entries of a kSmallMaxP system that a thread of NT owns (two at NT = 512,
+// three at NT = 256).
+template <int NT>
+constexpr int kTriOwned = (kSmallMaxP * (kSmallMaxP + 1) / 2 + NT - 1) / NT;
+
+// The entries owned by this thread: e = tid, tid + NT, ..., e = j (j + 1) / 2 + i -> (oi, oj) =
+// (i, j), owned where `on` and e lies in the triangle of p; av, the entries' values, zeroed.
+template <int NT, int H>
+__device__ __forceinline__ void chain_tri_owners(int p, bool on, bool (&own)[H], int (&oi)[H],
+                                                 int (&oj)[H], double (&av)[H]) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        av[h] = 0.0;
+        const int e = tid + h * NT;
+        own[h] = on && e < p * (p + 1) / 2;
+        int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+        while ((j + 1) * (j + 2) / 2 <= e) ++j;
+        while (j * (j + 1) / 2 > e) --j;
+        oj[h] = j;
+        oi[h] = e - j * (j + 1) / 2;
+    }
+}
+
+// A (its upper triangle in the owners' av) factored right-looking as A = U'U with one thread
+// per entry (i, j): per pivot k the owner of (k, k) takes the square root, the owners of row k
+// divide (row k of U goes to LDS, sU row-major), every trailing owner subtracts U(k, i) U(k, j)
+// -- the reference's operations entry by entry (BridgeRegression.cpp:560), two barriers per
+// pivot, which every thread of the workgroup reaches, and no register arrays.  A pivot that is
+// not positive sets error bit 8.  (One barrier per pivot -- trailing owners subtracting
+// a_ki a_kj / a_kk from a published unscaled row, one reciprocal square root per pivot --
+// measured the same at C1 in three alternations, 27 176-27 186 against 27 152-27 188 sweeps/s:
+// the factor is not what bounds the chain.)
+template <int H>
+__device__ __forceinline__ void chain_factor(int p, const bool (&own)[H], const int (&oi)[H],
+                                             const int (&oj)[H], double (&av)[H],
+                                             double (*sU)[kSmallMaxP + 1], uint32_t *err) {
+    for (int kk = 0; kk < p; ++kk) {
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+            if (own[h] && oi[h] == kk && oj[h] == kk) {
+                if (!(av[h] > 0.0)) atomicOr(err, 8u);
+                av[h] = sqrt(av[h]);
+                sU[kk][kk] = av[h];
+            }
+        __syncthreads();
+        const double d = sU[kk][kk];
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+            if (own[h] && oi[h] == kk && oj[h] > kk) {
+                av[h] = av[h] / d;
+                sU[kk][oj[h]] = av[h];
+            }
+        __syncthreads();
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+            if (own[h] && oi[h] > kk) av[h] -= sU[kk][oi[h]] * sU[kk][oj[h]];
+    }
+}
+
+// Wave 0, lane j holding entry j: w = m with U'v = c (forward), U m = v (backward), and z = x
+// with U x = z_in.  The caller forms beta = m + (its scale) x.
+__device__ __forceinline__ void chain_solves(int p, double (*sU)[kSmallMaxP + 1],
+                                             const double *c, const double *z_in, double &w,
+                                             double &z) {
+    const int lane = threadIdx.x & 63;
+    w = lane < p ? c[lane] : 0.0;
+    z = lane < p ? z_in[lane] : 0.0;
+    for (int kk = 0; kk < p; ++kk) {
+        const double vk = readlane_f64(w, kk) / sU[kk][kk];
+        if (lane > kk && lane < p) w -= sU[kk][lane] * vk;
+        if (lane == kk) w = vk;
+    }
+    for (int kk = p - 1; kk >= 0; --kk) {
+        const double ukk = sU[kk][kk];
+        const double mk = readlane_f64(w, kk) / ukk;
+        const double xk = readlane_f64(z, kk) / ukk;
+        if (lane < kk) {
+            const double ulk = sU[lane][kk];
+            w -= ulk * mk;
+            z -= ulk * xk;
+        }
+        if (lane == kk) {
+            w = mk;
+            z = xk;
+        }
+    }
+}
+
+// alpha | beta, tau in wave 0, whose lanes hold the beta they just wrote to sb: the proposal
+// from ua[0], the two sums over the coefficients, the decision on lane 0 (out of line) from
+// ua[1] under the prior (pr_a, pr_b), lbc = log B(pr_a, pr_b); into s_alpha and the trace slot.
+__device__ __forceinline__ void chain_alpha_step(int p, const double *sb, double tau,
+                                                 double alpha, const double (&ua)[2], double pr_a,
+                                                 double pr_b, const double &lbc, double &s_alpha,
+                                                 int slot, double *tr_alpha) {
+    const int lane = threadIdx.x & 63;
+    const double a_old = alpha;
+    double d_new;
+    const double a_new = alpha_propose(a_old, ua[0], d_new);
+    double sn = 0.0, so = 0.0;
+    if (lane < p) {
+        const double si = log(fabs(sb[lane] / tau));
+        sn = exp(a_new * si);
+        so = exp(a_old * si);
+    }
+    sn = wave_sum_all(sn);
+    so = wave_sum_all(so);
+    if (lane == 0) {
+        const double an =
+            alpha_mh_decide(a_old, a_new, d_new, sn, so, (double)p, pr_a, pr_b, lbc, ua[1]);
+        s_alpha = an;
+        if (slot >= 0) tr_alpha[slot] = an;
     }
 }
 

@@ -27,8 +27,9 @@
 // rows (a multiple of 4, so the four interleaved partial sums take the same rows in the same
 // order as over a resident X).
 //
-// The factor and the two solves are small_chain_body's (bb_small_body.h) with sig2 = 1: a
-// second copy, kept apart so that the small chain's kernels keep their code identity.
+// The entry ownership, the factor, the solves and the alpha step are bb_chain_steps.h's, shared
+// with small_chain_body (bb_small_body.h, whose look-ahead depth and LDS budget this file takes
+// too); sig2 = 1.
 #include <hip/hip_runtime.h>
 
 #include "bb_pg.h"
@@ -125,22 +126,12 @@ __global__ __launch_bounds__(NT, 2) void k_logit_chains(
     const double alpha0 = sc->alpha;
     __syncthreads();
     const double tau_shape = hy.nu_shape + ((double)p) / alpha0;
-    // upper-triangle entries owned by this thread: e = tid, tid + NT, e = j (j + 1) / 2 + i
-    constexpr int H = (kSmallMaxP * (kSmallMaxP + 1) / 2 + NT - 1) / NT;
+    // upper-triangle entries of A owned by this thread
+    constexpr int H = kTriOwned<NT>;
     bool own[H];
     int oi[H], oj[H];
     double av[H];
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-        av[h] = 0.0;
-        const int e = tid + h * NT;
-        own[h] = e < p * (p + 1) / 2;
-        int j = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-        while ((j + 1) * (j + 2) / 2 <= e) ++j;
-        while (j * (j + 1) / 2 > e) --j;
-        oj[h] = j;
-        oi[h] = e - j * (j + 1) / 2;
-    }
+    chain_tri_owners<NT>(p, true, own, oi, oj, av);
     for (int k = 0; k < count; ++k) {
         if (k % kSmallPre == 0) {
             // the counter-only variates of the next kSmallPre sweeps: wave 0 tau's gamma
@@ -241,72 +232,16 @@ __global__ __launch_bounds__(NT, 2) void k_logit_chains(
                     av[h] = g + (oi[h] == oj[h] ? sl[oi[h]] / dl : 0.0);
                 }
         }
-        // ---- beta | rest: the factor and solves of small_chain_body, sig2 = 1 ----
-        for (int kk = 0; kk < p; ++kk) {
-#pragma unroll
-            for (int h = 0; h < H; ++h)
-                if (own[h] && oi[h] == kk && oj[h] == kk) {
-                    if (!(av[h] > 0.0)) atomicOr(err, 8u);
-                    av[h] = sqrt(av[h]);
-                    sU[kk][kk] = av[h];
-                }
-            __syncthreads();
-            const double d = sU[kk][kk];
-#pragma unroll
-            for (int h = 0; h < H; ++h)
-                if (own[h] && oi[h] == kk && oj[h] > kk) {
-                    av[h] = av[h] / d;
-                    sU[kk][oj[h]] = av[h];
-                }
-            __syncthreads();
-#pragma unroll
-            for (int h = 0; h < H; ++h)
-                if (own[h] && oi[h] > kk) av[h] -= sU[kk][oi[h]] * sU[kk][oj[h]];
-        }
+        // ---- beta | rest: A = U'U, then wave 0's solves; sig2 = 1 ----
+        chain_factor(p, own, oi, oj, av, sU, err);
         if (wid == 0) {
-            // m: U'v = c (forward), U m = v (backward); x: U x = z; lane j holds entry j
-            double w = lane < p ? sc_[lane] : 0.0;
-            double z = lane < p ? s_z[kp][lane] : 0.0;
-            for (int kk = 0; kk < p; ++kk) {
-                const double vk = readlane_f64(w, kk) / sU[kk][kk];
-                if (lane > kk && lane < p) w -= sU[kk][lane] * vk;
-                if (lane == kk) w = vk;
-            }
-            for (int kk = p - 1; kk >= 0; --kk) {
-                const double ukk = sU[kk][kk];
-                const double mk = readlane_f64(w, kk) / ukk;
-                const double xk = readlane_f64(z, kk) / ukk;
-                if (lane < kk) {
-                    const double ulk = sU[lane][kk];
-                    w -= ulk * mk;
-                    z -= ulk * xk;
-                }
-                if (lane == kk) {
-                    w = mk;
-                    z = xk;
-                }
-            }
+            double w, z;
+            chain_solves(p, sU, sc_, s_z[kp], w, z);
             if (lane < p) sb[lane] = w + z;
-            if constexpr (MH) {
-                // ---- alpha | beta, tau: the lanes of wave 0 hold the beta they just wrote ----
-                const double a_old = alpha;
-                double d_new;
-                const double a_new = alpha_propose(a_old, s_ua[kp][0], d_new);
-                double sn = 0.0, so = 0.0;
-                if (lane < p) {
-                    const double si = log(fabs(sb[lane] / tau));
-                    sn = exp(a_new * si);
-                    so = exp(a_old * si);
-                }
-                sn = wave_sum_all(sn);
-                so = wave_sum_all(so);
-                if (lane == 0) {
-                    const double an = alpha_mh_decide(a_old, a_new, d_new, sn, so, (double)p, pr_a,
-                                                      pr_b, s_lbc, s_ua[kp][1]);
-                    s_alpha = an;
-                    if (slot >= 0) tr_alpha[slot] = an;
-                }
-            }
+            // ---- alpha | beta, tau: the lanes of wave 0 hold the beta they just wrote ----
+            if constexpr (MH)
+                chain_alpha_step(p, sb, tau, alpha, s_ua[kp], pr_a, pr_b, s_lbc, s_alpha, slot,
+                                 tr_alpha);
         }
         __syncthreads();
         if (slot >= 0 && tid < p) tr_beta[(size_t)slot * p + tid] = sb[tid];

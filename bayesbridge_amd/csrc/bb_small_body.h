@@ -1,10 +1,12 @@
 // bb_small_body.h -- the sweep loop of the fused small-p chain (bb_small.hip's header comment),
 // shared by its two translation units: bb_small.hip (alpha known) and bb_small_mh.hip (alpha
 // sampled).  They are two code objects, so that the out-of-line MH decision below is no part of
-// the known-alpha kernels' code identity (bayesbridge_amd/_kernel_code.py).  The sweep's first
-// steps (sums, tau and sig2, lambda, the orthogonal beta) are bb_chain_steps.h's, shared with
-// the wide and the triangle chains; the look-ahead, the factor and solves and the MH step are
-// here.
+// the known-alpha kernels' code identity (bayesbridge_amd/_kernel_code.py).  The sweep's steps
+// are bb_chain_steps.h's: the first (sums, tau and sig2, lambda, the orthogonal beta) shared
+// with the wide and the triangle chains, the last (the factor and the MH step) with the logistic
+// chain.  Here are the staging of X and G, the look-ahead, the entries of A, the order and
+// barriers of the sweep, and two steps written out that restate bb_chain_steps.h's templates
+// (entry ownership and the solves: called, they cost these kernels speed).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,18 +16,8 @@ namespace bb {
 
 namespace {
 
-constexpr int kSmallMaxP = kSmallChainMaxP;
 constexpr size_t kSmallXLds = 112 * 1024;  // X staged in LDS up to this size
 constexpr int kSmallPre = 32;  // sweeps of counter-only variates drawn ahead
-
-// alpha_mh_accept (bb_sampler.h) out of line: one thread's scalar work, whose registers are
-// then not the sweep loop's (inlined, the MH instances spill 122-125 VGPRs and take 504-520 B
-// of scratch per lane; so, 5-8 and 40-56).
-[[maybe_unused]] __device__ __noinline__ double alpha_mh_decide(double a_old, double a_new, double d_new,
-                                               double Sn, double So, double pp, double pr_a,
-                                               double pr_b, double lbc, double u1) {
-    return alpha_mh_accept(a_old, a_new, d_new, Sn, So, pp, pr_a, pr_b, lbc, u1);
-}
 
 }  // namespace
 
@@ -96,9 +88,10 @@ __device__ __forceinline__ void small_chain_body(
     __syncthreads();
     const double tau_shape = hy.nu_shape + ((double)p) / alpha0;
     const double sig2_shape = hy.sig2_shape + 0.5 * (double)n;
-    // upper-triangle entries owned by this thread: e = tid, tid + NT, ..., e = j (j + 1) / 2 + i
-    // (two per thread at NT = 512, three at NT = 256)
-    constexpr int H = (kSmallMaxP * (kSmallMaxP + 1) / 2 + NT - 1) / NT;
+    // upper-triangle entries of A owned by this thread (none: orthogonal design).  Written out:
+    // chain_tri_owners<NT>(p, !ortho, own, oi, oj, av) restated (bb_chain_steps.h; called, the
+    // packed instances ran 0.4-0.7 % slower)
+    constexpr int H = kTriOwned<NT>;
     bool own[H];
     int oi[H], oj[H];
     double av[H];
@@ -160,16 +153,9 @@ __device__ __forceinline__ void small_chain_body(
         if (ortho) {
             chain_beta_ortho(p, sb, sc_, sgd, sl, s_z[kp], tau, sig2);
         } else {
-            // A = G + diag(lambda sig2 / tau^2), factored right-looking as A = U'U with one
-            // thread per upper-triangle entry (i, j) (two for the last 16 at p = 32): per
-            // pivot k the owner of (k, k) takes the square root, the owners of row k divide
-            // (row k of U goes to LDS), every trailing owner subtracts U(k, i) U(k, j) -- the
-            // reference's operations entry by entry (BridgeRegression.cpp:560), two barriers
-            // per pivot and no register arrays.  (One barrier per pivot -- trailing owners
-            // subtracting a_ki a_kj / a_kk from a published unscaled row, one reciprocal square
-            // root per pivot -- measured the same at C1 in three alternations, 27 176-27 186
-            // against 27 152-27 188 sweeps/s, gpurun_out/r04q_*: the factor is not what bounds
-            // the chain.)
+            // A = G + diag(lambda sig2 / tau^2), an upper-triangle entry (i, j) per thread (two
+            // for the last 16 at p = 32), factored as A = U'U; wave 0 solves for the mean and
+            // the draw
             const double dl = tau * tau;
 #pragma unroll
             for (int h = 0; h < H; ++h)
@@ -177,29 +163,10 @@ __device__ __forceinline__ void small_chain_body(
                     const int i = oi[h], j = oj[h];
                     av[h] = sG[i][j] + (i == j ? sl[i] * sig2 / dl : 0.0);
                 }
-            for (int kk = 0; kk < p; ++kk) {
-#pragma unroll
-                for (int h = 0; h < H; ++h)
-                    if (own[h] && oi[h] == kk && oj[h] == kk) {
-                        if (!(av[h] > 0.0)) atomicOr(err, 8u);
-                        av[h] = sqrt(av[h]);
-                        sU[kk][kk] = av[h];
-                    }
-                __syncthreads();
-                const double d = sU[kk][kk];
-#pragma unroll
-                for (int h = 0; h < H; ++h)
-                    if (own[h] && oi[h] == kk && oj[h] > kk) {
-                        av[h] = av[h] / d;
-                        sU[kk][oj[h]] = av[h];
-                    }
-                __syncthreads();
-#pragma unroll
-                for (int h = 0; h < H; ++h)
-                    if (own[h] && oi[h] > kk) av[h] -= sU[kk][oi[h]] * sU[kk][oj[h]];
-            }
+            chain_factor(p, own, oi, oj, av, sU, err);
             if (wid == 0) {
-                // m: U'v = c (forward), U m = v (backward); x: U x = z; lane j holds entry j
+                // written out: chain_solves(p, sU, sc_, s_z[kp], w, z) restated (called, the
+                // single chains ran 0.5-1.4 % slower, the packed instances 1.1-1.3 %)
                 double w = lane < p ? sc_[lane] : 0.0;
                 double z = lane < p ? s_z[kp][lane] : 0.0;
                 for (int kk = 0; kk < p; ++kk) {
@@ -226,25 +193,9 @@ __device__ __forceinline__ void small_chain_body(
         }
         if constexpr (MH) {
             // ---- alpha | beta, tau: the lanes of wave 0 hold the beta they just wrote ----
-            if (wid == 0) {
-                const double a_old = alpha;
-                double d_new;
-                const double a_new = alpha_propose(a_old, s_ua[kp][0], d_new);
-                double sn = 0.0, so = 0.0;
-                if (lane < p) {
-                    const double si = log(fabs(sb[lane] / tau));
-                    sn = exp(a_new * si);
-                    so = exp(a_old * si);
-                }
-                sn = wave_sum_all(sn);
-                so = wave_sum_all(so);
-                if (lane == 0) {
-                    const double an = alpha_mh_decide(a_old, a_new, d_new, sn, so, (double)p, pr_a,
-                                                      pr_b, s_lbc, s_ua[kp][1]);
-                    s_alpha = an;
-                    if (slot >= 0) tr_alpha[slot] = an;
-                }
-            }
+            if (wid == 0)
+                chain_alpha_step(p, sb, tau, alpha, s_ua[kp], pr_a, pr_b, s_lbc, s_alpha, slot,
+                                 tr_alpha);
         }
         __syncthreads();
         SMALL_PHASE(4);

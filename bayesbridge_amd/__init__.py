@@ -330,6 +330,17 @@ def set_fused_alpha(on: bool) -> bool:
     return bool(library().bb_set_tuning(26, 1 if on else 0))
 
 
+def set_fused_tri_alpha(on: bool) -> bool:
+    """Switch alpha sampling inside the fused triangle-mixture chains (bb_set_tuning key 27,
+    default off) and return the previous setting.  While on, triangle-mixture engines and chain
+    batches created with P <= 32, P <= N and alpha unknown (``alpha <= 0``; general or
+    orthogonal design, one device) run whole sweeps, the alpha Metropolis-Hastings step included,
+    in one workgroup, a batch as one launch of a workgroup per chain; what already exists keeps
+    the path it was created with.  The kernel adds the sums of the alpha step in another order
+    than the general path, so a chain under the switch is not bit for bit the one without it."""
+    return bool(library().bb_set_tuning(27, 1 if on else 0))
+
+
 def chol_version() -> int:
     """The device Cholesky chain variant in use (bb_set_chol_version(0) reports it)."""
     return int(library().bb_set_chol_version(0))
@@ -579,7 +590,9 @@ def bridge_reg_tri_chains(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0, sig2_
     ``.C("bridge_regression_chains", ...)``: chain c is exactly what the c-th of ``nchains``
     consecutive ``bridge_reg_tri`` calls would return.  Small designs (P <= 32, P <= N, alpha
     known) run every chain side by side in one launch per block of sweeps, the SVD of X done
-    once.
+    once.  With alpha unknown (``alpha <= 0``) they do so after ``set_fused_tri_alpha(True)``,
+    each chain sampling its alpha inside the launch; without it the chains run one after another
+    on the general path.
 
     Returns a dict: beta, u, w (omega), shape (K x M x P), sig2, tau, alpha (K x M), runtime
     (one number for the batch).
@@ -711,7 +724,9 @@ def bridge_reg_tri_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.
                                   alpha_b=1.0, sig2_true=0.0, tau_true=0.0, burn=500,
                                   ortho=False, betaburn=0, maxlag=None):
     """``bridge_reg_tri_chains`` returning posterior summaries instead of traces, through
-    ``.C("bridge_regression_chains_summary", ...)``; see ``bridge_reg_stb_chains_summary``."""
+    ``.C("bridge_regression_chains_summary", ...)``; see ``bridge_reg_stb_chains_summary``.
+    With alpha unknown (``alpha <= 0``) the chains run as one batch after
+    ``set_fused_tri_alpha(True)`` (P <= 32, P <= N), else one after another."""
     return _chains_summary("bridge_reg_tri_chains_summary", True, y, X, nsamp, nchains, alpha,
                            sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
                            sig2_true, tau_true, burn, ortho, betaburn, maxlag)
@@ -1519,7 +1534,9 @@ class ChainBatch:
     together by one launch per run (bb_chains_*).  Chain c draws under the key
     (cfg.seed, cfg.stream + c); cfg.trace_capacity is each chain's ring capacity.
     cfg.method = 4 makes it a triangle-mixture batch (omega is the trace's ``lambda``; u and
-    shape through tri_trace / set_tri_state).  A stable-mixture batch needs P <= 32, or
+    shape through tri_trace / set_tri_state; P <= 32, P <= N; with cfg.true_alpha <= 0 it needs
+    ``set_fused_tri_alpha(True)`` at creation and each chain then samples its alpha inside the
+    launch, under the prior ``run``'s mcmc_phase selects).  A stable-mixture batch needs P <= 32, or
     P <= 128 when created after ``set_wide_chains(True)`` (it then keeps the wide kernel); with
     cfg.true_alpha <= 0 it needs P <= 32 and ``set_fused_alpha(True)`` at creation, and each
     chain then samples its alpha inside the launch (``run``'s mcmc_phase selects the prior).

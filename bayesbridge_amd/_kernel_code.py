@@ -114,12 +114,13 @@ def code_shas(so_path: str | None = None) -> dict:
 def mangled_prefix(instance: str) -> str:
     """bb::k_lambda_xu<8, 8> -> _ZN2bb11k_lambda_xuILi8ELi8EEEv (int / bool template
     arguments; a template kernel's mangling carries its void return type); bb::k_pre ->
-    _ZN2bb5k_preE."""
-    m = re.match(r"bb::(\w+)(?:<(.*)>)?$", instance.strip())
+    _ZN2bb5k_preE; a kernel of a translation unit's unnamed namespace, as rocprofv3 names it:
+    bb::(anonymous namespace)::k_tri_chain -> _ZN2bb12_GLOBAL__N_111k_tri_chainE."""
+    m = re.match(r"bb::(\(anonymous namespace\)::)?(\w+)(?:<(.*)>)?$", instance.strip())
     if not m:
         raise ValueError(f"not a bb:: kernel instance: {instance!r}")
-    base, args = m.group(1), m.group(2)
-    s = f"_ZN2bb{len(base)}{base}"
+    anon, base, args = m.group(1), m.group(2), m.group(3)
+    s = f"_ZN2bb{'12_GLOBAL__N_1' if anon else ''}{len(base)}{base}"
     if args is None:
         return s + "E"
     s += "I"

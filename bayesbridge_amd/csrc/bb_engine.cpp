@@ -134,6 +134,11 @@ int g_chains_wide = 0;
 // bb_small.hip with the alpha MH step inside (bb_small_mh.hip's instances, 512 threads) instead
 // of the general path
 int g_fused_alpha = 0;
+// bb_set_tuning key 27: triangle-mixture engines and chain batches created from now on with
+// p <= 32, p <= n and alpha unknown (general or orthogonal design, one device) run the fused
+// sweeps of bb_tri.hip with the alpha MH step inside (bb_tri_mh.hip's instances) instead of the
+// general path
+int g_fused_tri_alpha = 0;
 static const char *kPhaseNames[PH_COUNT] = {"pre", "scalars", "lambda", "pg", "ozprep", "gram",
                                             "xu", "reduce", "form", "chol", "solve", "beta",
                                             "xb", "alpha", "nid", "eapply", "end"};
@@ -1489,8 +1494,11 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
               c.p <= kWideChainMaxP && (c.p <= c.n || e->ortho()) && c.world == 1 &&
               e->hy.know_alpha && e->cvec && e->gdiag && (e->ortho() || e->G);
     if (e->wide) e->fused = true;
-    if (e->tri())  // bb_tri.hip k_tri_chain (general and orthogonal designs)
-        e->fused = c.p <= kTriChainMaxP && c.world == 1 && e->hy.know_alpha &&
+    // bb_tri.hip k_tri_chain (general and orthogonal designs); alpha sampled in the kernel where
+    // key 27 asks for it (bb_tri_mh.hip, p <= n as its batch)
+    if (e->tri())
+        e->fused = c.p <= kTriChainMaxP && c.world == 1 &&
+                   (e->hy.know_alpha || (g_fused_tri_alpha && c.p <= c.n)) &&
                    (!c.ortho || (e->tri_G && e->cvec));
     if (e->nid) nid_certify_lambda(e);
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -1659,7 +1667,9 @@ const char *chains_refusal(const bb_config &c) {
         static_assert(kTriChainMaxP == 32, "the message below says 32");
         if (c.p > kTriChainMaxP) return "a triangle chain batch needs p <= 32";
         if (c.p > c.n) return "a triangle chain batch needs p <= n";
-        if (!(c.true_alpha > 0)) return "a chain batch needs alpha known (true_alpha > 0)";
+        // bb_set_tuning key 27: bb_tri_mh.hip's instances sample alpha
+        if (!(c.true_alpha > 0) && !g_fused_tri_alpha)
+            return "a chain batch needs alpha known (true_alpha > 0)";
         return nullptr;
     }
     if (c.method == LOGIT) {  // the logistic bridge: bb_logit_chain.hip, alpha known or sampled
@@ -2312,7 +2322,8 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
                     b->proto->hy.know_alpha;
         // more triangle chains than the 512-thread instance holds at once (one per CU): a
         // narrower instance, several per CU, the same bits
-        if (b->tri()) b->threads = tri_chains_threads(c.n, c.p, nchains, cus);
+        if (b->tri())
+            b->threads = tri_chains_threads(c.n, c.p, nchains, cus, !b->proto->hy.know_alpha);
         auto &o = b->owned;
         const size_t K = (size_t)nchains, p = (size_t)c.p, cap = (size_t)b->cap;
         b->beta = dalloc<double>(K * p, o);
@@ -2350,7 +2361,9 @@ int bb_chains_count(const bb_chains *b) { return b->K; }
 
 int bb_chains_resident_per_cu(const bb_chains *b) {
     if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
-    if (b->tri()) return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads);
+    if (b->tri())
+        return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads,
+                                          !b->proto->hy.know_alpha);
     if (b->logit())
         return logit_chains_resident_per_cu(b->proto->n, b->p, !b->proto->hy.know_alpha);
     if (b->wide) return wide_chains_resident_per_cu(b->p);
@@ -2364,7 +2377,7 @@ int bb_chains_threads(const bb_chains *b) {
 
 int bb_chains_set_threads(bb_chains *b, int threads) {
     if (!b->tri() || hipSetDevice(b->proto->cfg.device) != hipSuccess ||
-        tri_chains_resident_per_cu(b->proto->n, b->p, threads) < 0) {
+        tri_chains_resident_per_cu(b->proto->n, b->p, threads, !b->proto->hy.know_alpha) < 0) {
         set_error("bb_chains_set_threads: no triangle chain-batch instance of %d threads", threads);
         return -1;
     }
@@ -2378,7 +2391,7 @@ int bb_chains_init_state(bb_chains *b) {
 
 int bb_chains_run(bb_chains *b, uint64_t t0, int count, int first_slot, int slot_step,
                   int mcmc_phase) {
-    // mcmc_phase selects the prior of the alpha MH step (batches created under key 26)
+    // mcmc_phase selects the prior of the alpha MH step (batches created under key 26 or 27)
     return guarded(b->proto->cfg.device, [&] {
         b->run(t0, count, first_slot, slot_step, mcmc_phase);
         HIPCHECK(hipGetLastError());
@@ -3508,7 +3521,8 @@ int bb_set_tuning(int key, int value) {
                  {9, &g_shard_proto, 1}, {10, &g_nid_mixed, 1}, {11, &g_nid_poll, 1},
                  {12, &g_rs_xcd, 1},    {13, &g_lam_wave, 1},  {15, &g_lam_lend, 1},
                  {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1},
-                 {24, &g_nid_b32, 2},   {25, &g_chains_wide, 1}, {26, &g_fused_alpha, 1}};
+                 {24, &g_nid_b32, 2},   {25, &g_chains_wide, 1}, {26, &g_fused_alpha, 1},
+                 {27, &g_fused_tri_alpha, 1}};
     for (const auto &k : kKeys)
         if (k.key == key) {
             const int old = *k.var;

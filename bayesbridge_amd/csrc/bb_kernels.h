@@ -455,7 +455,7 @@ struct ChainTraces {
 };
 // `count` sweeps under the key (k0, k1) (chain c of a batch: (k0, k1 + c)): sweep k uses counter
 // t0 + k and trace slot (first_slot + k slot_step) % cap (first_slot < 0: none).
-// (pr_a, pr_b): the Beta prior of the small chain's alpha MH step in this launch's phase (the
+// (pr_a, pr_b): the Beta prior of the fused chains' alpha MH step in this launch's phase (the
 // engine's alpha_prior_a; unused where alpha is known).
 struct ChainRun {
     uint64_t k0, k1, t0;
@@ -512,9 +512,12 @@ int wide_chains_threads(int p);
 // variates
 constexpr int kWideBlock = 16;
 
-// Whole triangle-mixture sweeps (alpha known, p <= kTriChainMaxP) in one single-workgroup
-// launch (bb_tri.hip k_tri_chain): S_alpha / rss, tau and sig2, then omega, u and the
-// rtnorm_gibbs passes of launch_tri_update in one wave.
+// Whole triangle-mixture sweeps (p <= kTriChainMaxP) in one single-workgroup launch (bb_tri.hip
+// k_tri_chain): S_alpha / rss, tau and sig2, then omega, u and the rtnorm_gibbs passes of
+// launch_tri_update in one wave; with alpha known, or (d.hy.know_alpha == 0: engines and batches
+// created under bb_set_tuning key 27) sampled by the MH step of launch_alpha_mh after the
+// sweep's last beta, under the prior (r.pr_a, r.pr_b) -- bb_tri_mh.hip's k_tri_chain_mh /
+// k_tri_chains_mh.
 constexpr int kTriChainMaxP = 32;
 void launch_tri_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
                       const ChainTraces &tr, const ChainRun &r);
@@ -523,12 +526,14 @@ void launch_tri_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
 // (k_tri_chains).  `threads` names the instance: 512 (the single chain's LDS layout), or 256 or
 // 128, which keep 512 virtual threads and size their LDS by p, so that several chains share a
 // CU; every instance gives the single chain's bits.  Returns -1 if there is no such instance.
-// tri_chains_resident_per_cu: the workgroups of that instance the runtime keeps resident on one
-// CU for an n x p design (-1 if the query fails).
+// Where alpha is sampled (d.hy.know_alpha == 0) the launch runs k_tri_chains_mh of the same
+// threads.  tri_chains_resident_per_cu: the workgroups of that instance (mh: of its
+// alpha-sampling twin) the runtime keeps resident on one CU for an n x p design (-1 if the query
+// fails).
 int launch_tri_chains(hipStream_t s, int nchains, int threads, const ChainDesign &d,
                       const ChainState &c, const ChainTraces &tr, const ChainRun &r);
-int tri_chains_resident_per_cu(int n, int p, int threads);
-int tri_chains_threads(int n, int p, int nchains, int cus);  // the instance a batch runs
+int tri_chains_resident_per_cu(int n, int p, int threads, int mh);
+int tri_chains_threads(int n, int p, int nchains, int cus, int mh);  // the instance a batch runs
 
 // Posterior summaries of trace rings on the device (bb_summary.hip): per chain c
 // and parameter q (beta_1..beta_p, then sig2, tau, alpha) the running sums from which the mean,

@@ -18,183 +18,14 @@
 // r.tnorm comes from the un-vendored RNG library; it is restated from Robert (1995):
 // normal or uniform rejection when the standardised interval holds 0, else Robert's
 // uniform / translated-exponential proposal.  Counter kinds 8 (omega), 9 (u), 10 (z_i).
+// The draws and the fused chain's sweep body are bb_tri_body.h's, shared with bb_tri_mh.hip.
 #include <hip/hip_runtime.h>
 
-#include "bb_chain_steps.h"
+#include "bb_tri_body.h"
 
 namespace bb {
 
 namespace {
-
-constexpr int kTriNT = 256;
-constexpr int kTriE = kTriMaxP / kTriNT;  // coefficients per thread
-constexpr long kTnMaxAttempts = 1l << 22;
-constexpr unsigned KIND_TRI_OMEGA = 8, KIND_TRI_U = 9, KIND_TRI_Z = 10;
-
-// Attempt 0 of every coordinate's draw is precomputed in parallel before the coordinate
-// loop (pre = {r0, r1, Box-Muller normal of (r0, r1)}), so the serial chain only runs
-// Philox on a rejection.  Bit-identical to drawing it in place.
-struct Pre {
-    double r0, r1, x0;
-};
-
-__device__ __forceinline__ void attempt(Key key, uint64_t t, uint64_t i, uint64_t it, long k,
-                                        const Pre &pre, double &r0, double &r1, double &x0,
-                                        bool need_x) {
-    if (k == 0) {
-        r0 = pre.r0;
-        r1 = pre.r1;
-        x0 = pre.x0;
-    } else {
-        U4 r = uniforms(key, t, KIND_TRI_Z, i, it, (uint64_t)k);
-        r0 = r.r[0];
-        r1 = r.r[1];
-        x0 = need_x ? bm_normal(r0, r1) : 0.0;
-    }
-}
-
-// Force-inlined: the compiler outlined tnorm, and an out-of-line call inside the
-// coordinate loop costs its prologue's s_waitcnt vmcnt(0), which drains the row prefetch
-// on every coordinate.  k0 > 0 resumes the rejection loop at attempt k0 (k_tri_chain's
-// fall-through after its parallel attempts; `pre` is then unused).
-// LOST (k_tri_chains): a standardised bound beyond ~1e154 overflows a * a, the threshold is
-// NaN and no attempt can be accepted; the draw then takes the loop's outcome (flag 64, the
-// bound itself) at once instead of after kTnMaxAttempts rounds on a CU other chains wait for.
-template <bool LOST = false>
-__device__ __forceinline__ double tn_pos(double a, double b, Key key, uint64_t t, uint64_t i,
-                                         uint64_t it, const Pre &pre, uint32_t *err,
-                                         long k0 = 0) {
-    const double sq = sqrt(a * a + 4.0);
-    const double as = 0.5 * (a + sq);
-    const double thr = a + 2.0 / (a + sq) * exp(0.5 + 0.25 * (a * a - a * sq));
-    if (LOST && thr != thr) {
-        atomicOr(err, 64u);
-        return a;
-    }
-    for (long k = k0; k < kTnMaxAttempts; ++k) {
-        double r0, r1, x0;
-        attempt(key, t, i, it, k, pre, r0, r1, x0, false);
-        if (b <= thr) {
-            const double x = a + (b - a) * r0;
-            if (r1 <= exp(0.5 * (a * a - x * x))) return x;
-        } else {
-            const double x = a - log(r0) / as;
-            const double e = x - as;
-            if (x <= b && r1 <= exp(-0.5 * e * e)) return x;
-        }
-    }
-    atomicOr(err, 64u);
-    return a;
-}
-
-template <bool LOST = false>
-__device__ __forceinline__ double tnorm(double lo, double hi, double mu, double sd, Key key,
-                                        uint64_t t, uint64_t i, uint64_t it, const Pre &pre,
-                                        uint32_t *err, long k0 = 0) {
-    const double a = (lo - mu) / sd, b = (hi - mu) / sd;
-    if (!(a < b)) {
-        atomicOr(err, 128u);
-        return lo;
-    }
-    if (a <= 0.0 && b >= 0.0) {
-        const bool wide = (b - a) >= 2.5066282746310002;  // sqrt(2 pi)
-        for (long k = k0; k < kTnMaxAttempts; ++k) {
-            double r0, r1, x0;
-            attempt(key, t, i, it, k, pre, r0, r1, x0, wide);
-            if (wide) {
-                if (x0 >= a && x0 <= b) return mu + sd * x0;
-            } else {
-                const double x = a + (b - a) * r0;
-                if (r1 <= exp(-0.5 * x * x)) return mu + sd * x;
-            }
-        }
-        atomicOr(err, 64u);
-        return lo;
-    }
-    if (a > 0.0) return mu + sd * tn_pos<LOST>(a, b, key, t, i, it, pre, err, k0);
-    return mu - sd * tn_pos<LOST>(-b, -a, key, t, i, it, pre, err, k0);
-}
-
-// The same draw with attempts 0 .. K-1 evaluated in parallel, attempt k in lane k from its
-// precomputed (r0, r1, x0): the lowest accepted attempt is the sequential loop's answer;
-// if none of the K is accepted the loop resumes at attempt K.  lo, hi, mu, sd uniform; every
-// lane of the wave calls this.
-template <int K, bool LOST>
-__device__ __forceinline__ double tnorm_par(double lo, double hi, double mu, double sd,
-                                            double r0, double r1, double x0, Key key,
-                                            uint64_t t, uint64_t i, uint64_t it, uint32_t *err) {
-    const int lane = threadIdx.x & 63;
-    const double a = (lo - mu) / sd, b = (hi - mu) / sd;
-    if (!(a < b)) {
-        atomicOr(err, 128u);
-        return lo;
-    }
-    bool acc = false;
-    double val = 0.0;
-    if (a <= 0.0 && b >= 0.0) {
-        if ((b - a) >= 2.5066282746310002) {  // sqrt(2 pi)
-            acc = x0 >= a && x0 <= b;
-            val = mu + sd * x0;
-        } else {
-            const double x = a + (b - a) * r0;
-            acc = r1 <= exp(-0.5 * x * x);
-            val = mu + sd * x;
-        }
-    } else {
-        const double pa = a > 0.0 ? a : -b, pb = a > 0.0 ? b : -a;  // tn_pos's (a, b)
-        const double sq = sqrt(pa * pa + 4.0);
-        const double as = 0.5 * (pa + sq);
-        const double thr = pa + 2.0 / (pa + sq) * exp(0.5 + 0.25 * (pa * pa - pa * sq));
-        double x;
-        if (pb <= thr) {
-            x = pa + (pb - pa) * r0;
-            acc = r1 <= exp(0.5 * (pa * pa - x * x));
-        } else {
-            x = pa - log(r0) / as;
-            const double e = x - as;
-            acc = x <= pb && r1 <= exp(-0.5 * e * e);
-        }
-        val = a > 0.0 ? mu + sd * x : mu - sd * x;
-    }
-    const uint64_t m = __ballot(acc && lane < K);
-    if (m) return readlane_f64(val, __ffsll((unsigned long long)m) - 1);
-    return tnorm<LOST>(lo, hi, mu, sd, key, t, i, it, Pre{0.0, 0.0, 0.0}, err, K);
-}
-
-// Row-of-16 max / min through DPP (quad xor 1, quad xor 2, half-row mirror, row mirror):
-// every lane of a 16-lane row ends with the row's extreme.  v_max_f64 takes no DPP operand
-// on gfx9, so each step moves the two halves with v_mov_b32_dpp.  Replaces a 6-step
-// ds_bpermute butterfly per value (an LDS round trip per step).
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double row16_max(double v) {
-    v = fmax(v, dpp_d<0xB1>(v));
-    v = fmax(v, dpp_d<0x4E>(v));
-    v = fmax(v, dpp_d<0x141>(v));
-    return fmax(v, dpp_d<0x140>(v));
-}
-__device__ __forceinline__ double row16_min(double v) {
-    v = fmin(v, dpp_d<0xB1>(v));
-    v = fmin(v, dpp_d<0x4E>(v));
-    v = fmin(v, dpp_d<0x141>(v));
-    return fmin(v, dpp_d<0x140>(v));
-}
-
-// Combine the four row extremes of a wave (every lane holds its row's value) through
-// scalar reads of lanes 0, 16, 32, 48: the wave's extreme, uniform in every lane.
-__device__ __forceinline__ double rows_max(double v) {
-    return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)),
-                fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
-}
-__device__ __forceinline__ double rows_min(double v) {
-    return fmin(fmin(readlane_f64(v, 0), readlane_f64(v, 16)),
-                fmin(readlane_f64(v, 32), readlane_f64(v, 48)));
-}
 
 // tVc: tV column-major (tVc[i + j p] = tV(i, j)); tVr: its transpose (tVr[i p + j] =
 // tV(i, j)), so row i of tV is contiguous for the coordinate loop.
@@ -416,285 +247,6 @@ __global__ __launch_bounds__(kTriNT) void k_tri_update(
     }
 }
 
-// ---------------------------------------------------------------------------
-// Whole sweeps for small p (the reference's published designs, p = 10, 13): the general
-// path's four launches per sweep (S_alpha / X beta partials, tau and sig2, k_tri_update,
-// X beta) cost more than the arithmetic.  k_tri_chain keeps the chain in LDS and runs
-// `count` sweeps per launch: all 512 threads for S_alpha / rss, two lanes for tau and sig2,
-// then wave 0 alone (lane j = coefficient j) for omega, u and the coordinate passes, whose
-// bound reductions are DPP + readlane inside the wave (no barrier per coordinate) and whose
-// truncated-normal draws test kTcK attempts at once (tnorm_par).  While wave 0 runs the
-// serial part, waves 1..7 draw every counter-only variate of the NEXT sweep into the other
-// half of a double buffer: the tau / sig2 gamma variates, the omega / u uniforms and
-// attempts 0..kTcK-1 of each coordinate's first-pass truncated normal.  The arithmetic is
-// k_tri_update's, expression for expression.
-// ---------------------------------------------------------------------------
-constexpr int kTcNT = 512;
-constexpr int kTcK = 16;                // parallel truncated-normal attempts
-constexpr size_t kTcXLds = 96 * 1024;  // X staged in LDS up to this size
-constexpr int kTcP = kTriChainMaxP;
-
-// The counter-only variates of one sweep, in a buffer of tc_nvar(P) doubles laid out for P
-// coefficients (P = kTcP in the static buffers of the 512-thread instances, P = p in the
-// compact instance's dynamic LDS):
-//   [0] gt, [1] gs             Ga(tau shape, 1), Ga(sig2 shape, 1)
-//   om(j, 0..2), uu(j)         omega: r0 and the Ga(1, 1) / Ga(2, 1) variates; u
-//   r(i, k, 0..1), x(i, k)     attempt k of coordinate i (pass 0): r0, r1 and its Box-Muller normal
-struct TcVariates {
-    double *b;
-    int P;
-    __device__ __forceinline__ double &gt() const { return b[0]; }
-    __device__ __forceinline__ double &gs() const { return b[1]; }
-    __device__ __forceinline__ double &om(int j, int c) const { return b[2 + 3 * j + c]; }
-    __device__ __forceinline__ double &uu(int j) const { return b[2 + 3 * P + j]; }
-    __device__ __forceinline__ double &r(int i, int k, int c) const {
-        return b[2 + 4 * P + (i * kTcK + k) * 2 + c];
-    }
-    __device__ __forceinline__ double &x(int i, int k) const {
-        return b[2 + (4 + 2 * kTcK) * P + i * kTcK + k];
-    }
-};
-__host__ __device__ constexpr int tc_nvar(int P) { return 2 + (4 + 3 * kTcK) * P; }
-
-// Item e of sweep tt's variates (e < 2 + p (1 + kTcK)).
-__device__ __forceinline__ void tc_variate(const TcVariates &v, int e, int p, double tau_shape,
-                                           double sig2_shape, const Hyper &hy, Key key,
-                                           uint64_t tt, uint32_t *err) {
-    if (e == 0) {
-        if (!hy.know_tau) v.gt() = gamma1(tau_shape, key, tt, KIND_TAU, err);
-    } else if (e == 1) {
-        if (!hy.know_sig2) v.gs() = gamma1(sig2_shape, key, tt, KIND_SIG2, err);
-    } else if (e < 2 + p) {
-        const int j = e - 2;
-        const U4 r = uniforms(key, tt, KIND_TRI_OMEGA, (uint64_t)j, 0, 0);
-        v.om(j, 0) = r.r[0];
-        v.om(j, 1) = -log(r.r[1]);                // Ga(1, 1)
-        v.om(j, 2) = -log(r.r[1]) - log(r.r[2]);  // Ga(2, 1)
-        v.uu(j) = uniforms(key, tt, KIND_TRI_U, (uint64_t)j, 0, 0).r[0];
-    } else {
-        const int q = e - 2 - p, i = q / kTcK, k = q % kTcK;
-        const U4 r = uniforms(key, tt, KIND_TRI_Z, (uint64_t)i, 0, (uint64_t)k);
-        v.r(i, k, 0) = r.r[0];
-        v.r(i, k, 1) = r.r[1];
-        v.x(i, k) = bm_normal(r.r[0], r.r[1]);
-    }
-}
-
-// The whole sweep loop of one chain in one workgroup: k_tri_chain runs it once, k_tri_chains
-// once per workgroup on that chain's state, so the arithmetic exists once.
-// The sums and the tau / sig2 draws are bb_chain_steps.h's (chain_sums, chain_scalars).
-// NT: real threads (64 | NT | kTcNT).  The only order-dependent arithmetic outside wave 0 is the
-// S_alpha / rss reduction over kTcNT threads; a narrower workgroup keeps kTcNT VIRTUAL threads
-// (chain_sums<NT, kTcNT>), so red[.][0..7] hold the same bits and are summed in the same order.
-// The pre-drawn variates depend on their counters alone, so which thread draws them does not
-// matter.
-// COMPACT: the basis and the variate buffers live in the dynamic LDS behind X, sized by p
-// instead of kTcP, so that several workgroups share a CU's LDS.
-// LOST: a draw that can never be accepted gives up at once (tn_pos).
-template <int NT, bool COMPACT, bool LOST>
-__device__ __forceinline__ void tri_chain_body(
-    const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
-    const double *__restrict__ tVc, const double *__restrict__ tVr,
-    const double *__restrict__ av, const double *__restrict__ dv, const double *__restrict__ Gf,
-    const double *__restrict__ cv, int ortho, int x_lds, double *beta, double *u, double *omega,
-    double *shape, DevScalars *sc, Hyper hy, int betaburn, Key key, uint64_t t0, int count,
-    int first_slot, int slot_step, int cap, double *tr_beta, double *tr_u, double *tr_omega,
-    double *tr_shape, double *tr_sig2, double *tr_tau, double *tr_alpha, uint32_t *err) {
-    static_assert(NT % 64 == 0 && NT >= 128 && kTcNT % NT == 0, "NT divides kTcNT; wave 1 draws sig2");
-    extern __shared__ double sX[];
-    __shared__ double sT[COMPACT ? 1 : 2 * kTcP * kTcP];
-    __shared__ double sV[COMPACT ? 1 : 2 * tc_nvar(kTcP)];
-    __shared__ double sb[kTcP];
-    __shared__ double red[2][kTcNT / 64];
-    __shared__ double s_tau, s_sig2;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    // variate buffers laid out for VP coefficients; COMPACT: [X | sTc | sTr | vb0 | vb1]
-    const int VP = COMPACT ? p : kTcP, TP = COMPACT ? p * p : kTcP * kTcP;
-    double *const dyn = sX + (x_lds ? (size_t)n * p : 0);
-    double *const sTc = COMPACT ? dyn : sT;
-    double *const sTr = sTc + TP;
-    double *const vbase = COMPACT ? dyn + 2 * TP : sV;
-    auto vbuf = [&](int half) { return TcVariates{vbase + half * tc_nvar(VP), VP}; };
-    // orthogonal design: sTc holds the full symmetric Gram X'X (row j contiguous) instead
-    for (int e = tid; e < p * p; e += NT) {
-        sTc[e] = ortho ? Gf[e] : tVc[e];
-        if (!ortho) sTr[e] = tVr[e];
-    }
-    if (x_lds)
-        for (int e = tid; e < n * p; e += NT) sX[e] = X[(size_t)(e % n) + (size_t)(e / n) * ldx];
-    const double *Xs = x_lds ? sX : X;
-    const int lds_x = x_lds ? n : ldx;
-    const bool act = wid == 0 && lane < p;  // wave 0, lane j = coefficient / coordinate j
-    double uj = 0.0, om = 0.0, sh = 0.0, aj_c = 0.0, dj_c = 0.0;
-    if (tid < p) {
-        sb[tid] = beta[tid];
-        uj = u[tid];
-        aj_c = ortho ? cv[tid] : av[tid];          // ortho: c_j = (X'y)_j
-        dj_c = ortho ? Gf[(size_t)tid * p + tid] : dv[tid];  //        G_jj
-    }
-    if (tid == 0) {
-        s_tau = sc->tau;
-        s_sig2 = sc->sig2;
-    }
-    const double alpha = sc->alpha;
-    const double tau_shape = hy.nu_shape + ((double)p) / alpha;
-    const double sig2_shape = hy.sig2_shape + 0.5 * (double)n;
-    const int nvar = 2 + p * (1 + kTcK);
-    for (int e = tid; e < nvar; e += NT)  // sweep 0's variates
-        tc_variate(vbuf(0), e, p, tau_shape, sig2_shape, hy, key, t0, err);
-    __syncthreads();
-    for (int k = 0; k < count; ++k) {
-        const TcVariates v = vbuf(k & 1);
-        const uint64_t t = t0 + (uint64_t)k;
-        const int slot = first_slot < 0 ? -1 : (first_slot + k * slot_step) % cap;
-        chain_sums<NT, kTcNT>(Xs, lds_x, n, p, y, sb, alpha, red);
-        __syncthreads();
-        chain_scalars<kTcNT, true>(red, hy, alpha, [&] { return v.gt(); }, &v.gs(), s_tau, s_sig2,
-                                   slot, tr_tau, tr_sig2, tr_alpha);
-        __syncthreads();
-        if (wid > 0) {
-            // the next sweep's variates, off wave 0's serial chain
-            if (k + 1 < count)
-                for (int e = tid - 64; e < nvar; e += NT - 64)
-                    tc_variate(vbuf((k + 1) & 1), e, p, tau_shape, sig2_shape, hy, key, t + 1, err);
-        } else {
-            const double tau = s_tau, sig2 = s_sig2, sig = sqrt(sig2);
-            double bj = 0.0;
-            if (act) {
-                // sample_omega, sample_u, the bound of sample_beta (BridgeRegression.cpp:97-146,
-                // :410-412)
-                const double betaj = sb[lane];
-                const double aj = exp(alpha * log(fabs(betaj) / ((1.0 - uj) * tau)));
-                const double prob = alpha / (1.0 + alpha * aj);
-                double w;
-                if (v.om(lane, 0) > prob) {
-                    sh = 1.0;
-                    w = v.om(lane, 1);
-                } else {
-                    sh = 2.0;
-                    w = v.om(lane, 2);
-                }
-                om = w + aj;
-                const double right = 1.0 - fabs(betaj) / tau * exp(-1.0 * log(om) / alpha);
-                uj = right * v.uu(lane);
-                bj = (1.0 - uj) * exp(log(om) / alpha) * tau;
-                // A NaN bound (the chain's state is no longer finite) is no truncation
-                // interval.  The orthogonal pass reports it (tnorm's flag 128); the general
-                // pass would draw NaN after NaN from the flat branch below without a word,
-                // so a batch reports it here, in the chain's own flag word.
-                if (LOST && bj != bj) atomicOr(err, 128u);
-                if (slot >= 0) {
-                    tr_omega[(size_t)slot * p + lane] = om;
-                    tr_shape[(size_t)slot * p + lane] = sh;
-                    tr_u[(size_t)slot * p + lane] = uj;
-                }
-            }
-            if (ortho) {
-                // sample_beta_ortho (BridgeRegression.cpp:362-403), one coordinate pass as
-                // k_tri_update's: m_j = (c_j - sum_{k != j} G_jk beta_k) / G_jj, sd
-                // sqrt(sig2 / G_jj), truncated to |beta_j| <= b_j; attempts 0..kTcK-1 of
-                // every coordinate precomputed by waves 1..7 during the previous sweep
-                double bl = act ? sb[lane] : 0.0;
-                for (int j = 0; j < p; ++j) {
-                    const double prod = (act && lane != j) ? sTc[j * p + lane] * bl : 0.0;
-                    const double xb = wave_sum_all(prod);  // xor tree: the same bits in every lane
-                    const double gjj = readlane_f64(dj_c, j), bnd = readlane_f64(bj, j);
-                    const double m = (readlane_f64(aj_c, j) - xb) / gjj;
-                    const double sd = sqrt(sig2 / gjj);
-                    const int ka = lane < kTcK ? lane : 0;
-                    const double zn = tnorm_par<kTcK, LOST>(-1.0 * bnd, bnd, m, sd, v.r(j, ka, 0),
-                                                            v.r(j, ka, 1), v.x(j, ka), key, t,
-                                                            (uint64_t)j, 0, err);
-                    if (lane == j) bl = zn;
-                }
-                if (act) {
-                    sb[lane] = bl;
-                    if (slot >= 0) tr_beta[(size_t)slot * p + lane] = bl;
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            } else {
-            // conditional mean a_i / d_i^2 and sd sigma / d_i of coordinate i (lane i)
-            const bool ok = dj_c > 1e-16;
-            const double ci = ok ? aj_c / (dj_c * dj_c) : 0.0;
-            const double si = ok ? sig / dj_c : -1.0;
-            double zr = 0.0;
-            for (int it = 0; it <= betaburn; ++it) {
-                Pre pr{0.0, 0.0, 0.0};  // attempt 0 of coordinate `lane` (passes >= 1)
-                if (it > 0 && act) {
-                    const U4 q = uniforms(key, t, KIND_TRI_Z, (uint64_t)lane, (uint64_t)it, 0);
-                    pr = Pre{q.r[0], q.r[1], bm_normal(q.r[0], q.r[1])};
-                }
-                // z = tV beta (:246), then beta_cur = tV' z, in k_tri_update's order
-                zr = 0.0;
-                if (act)
-                    for (int j = 0; j < p; ++j) zr += sTc[lane + j * p] * sb[j];
-                double bc = 0.0;
-                for (int kk = 0; kk < p; ++kk) {
-                    const double zk = readlane_f64(zr, kk);
-                    if (act) bc += sTr[kk * p + lane] * zk;
-                }
-                for (int i = 0; i < p; ++i) {  // :250-283
-                    const double vi = act ? sTr[i * p + lane] : 0.0;
-                    const double zi = readlane_f64(zr, i);
-                    double lmax = -1.0 * 1.7976931348623157e308, rmin = 1.7976931348623157e308;
-                    if (act) {
-                        const double rji = bc - vi * zi;
-                        const double dif = bj - rji, sum = bj + rji;
-                        const double left = (vi > 0 ? -sum : -dif) / fabs(vi);
-                        const double right = (vi > 0 ? dif : sum) / fabs(vi);
-                        lmax = lmax > left ? lmax : left;
-                        rmin = rmin < right ? rmin : right;
-                    }
-                    const double L = rows_max(row16_max(lmax));
-                    const double R = rows_min(row16_min(rmin));
-                    const double sdi = readlane_f64(si, i);
-                    double zn;
-                    if (it == 0) {
-                        const int ka = lane < kTcK ? lane : 0;
-                        if (sdi > 0.0)
-                            zn = tnorm_par<kTcK, LOST>(L, R, readlane_f64(ci, i), sdi,
-                                                       v.r(i, ka, 0), v.r(i, ka, 1), v.x(i, ka),
-                                                       key, t, (uint64_t)i, 0, err);
-                        else
-                            zn = L + (R - L) * v.r(i, 0, 0);
-                    } else {
-                        const Pre pi{readlane_f64(pr.r0, i), readlane_f64(pr.r1, i),
-                                     readlane_f64(pr.x0, i)};
-                        if (sdi > 0.0)
-                            zn = tnorm<LOST>(L, R, readlane_f64(ci, i), sdi, key, t, (uint64_t)i,
-                                             (uint64_t)it, pi, err);
-                        else
-                            zn = L + (R - L) * pi.r0;
-                    }
-                    bc += vi * (zn - zi);
-                    if (lane == i) zr = zn;
-                }
-                // beta = tV' z (:285)
-                double bn = 0.0;
-                for (int kk = 0; kk < p; ++kk) {
-                    const double zk = readlane_f64(zr, kk);
-                    if (act) bn += sTr[kk * p + lane] * zk;
-                }
-                if (act) sb[lane] = bn;
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // sb read by other lanes next
-            }
-            if (act && slot >= 0) tr_beta[(size_t)slot * p + lane] = sb[lane];
-            }
-        }
-        __syncthreads();
-    }
-    if (act) {
-        beta[lane] = sb[lane];
-        u[lane] = uj;
-        omega[lane] = om;
-        shape[lane] = sh;
-    }
-    if (tid == 0) {
-        sc->tau = s_tau;
-        sc->sig2 = s_sig2;
-    }
-}
-
 __global__ __launch_bounds__(kTcNT) void k_tri_chain(
     const double *__restrict__ X, int ldx, int n, int p, const double *__restrict__ y,
     const double *__restrict__ tVc, const double *__restrict__ tVr,
@@ -896,13 +448,10 @@ const TriChainsInstance *tri_chains_instance(int threads) {
                                              {k_tri_chains<256, true>, 256, true},
                                              {k_tri_chains<128, true>, 128, true}};
     static const bool optin = [] {
-        for (const TriChainsInstance &i : inst) {
-            const size_t extra =
-                i.compact ? (2 * kTcP * kTcP + 2 * tc_nvar(kTcP)) * sizeof(double) : 0;
+        for (const TriChainsInstance &i : inst)
             (void)hipFuncSetAttribute((const void *)i.kern,
                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(kTcXLds + extra));
-        }
+                                      tri_chain_shm_max(i.compact));
         return true;
     }();
     (void)optin;
@@ -911,21 +460,12 @@ const TriChainsInstance *tri_chains_instance(int threads) {
     return nullptr;
 }
 
-// dynamic LDS of a launch: X when it fits under kTcXLds, and for a compact instance the basis
-// and the two variate buffers behind it, all sized by p
-size_t tri_chains_shm(const TriChainsInstance &i, int n, int p, int *x_lds) {
-    const size_t xbytes = (size_t)n * p * sizeof(double);
-    *x_lds = xbytes <= kTcXLds;
-    const size_t extra = i.compact ? (2 * (size_t)p * p + 2 * tc_nvar(p)) * sizeof(double) : 0;
-    return (*x_lds ? xbytes : 0) + extra;
-}
-
 // `blocks` workgroups of instance i (k_tri_chain has the kernels' type too): the structs
 // unpacked into its arguments
 void tri_launch(const TriChainsInstance &i, int blocks, hipStream_t s, const ChainDesign &d,
                 const ChainState &c, const ChainTraces &tr, const ChainRun &r) {
     int x_lds = 0;
-    const size_t shm = tri_chains_shm(i, d.n, d.p, &x_lds);
+    const size_t shm = tri_chain_shm(i.compact, d.n, d.p, &x_lds);
     i.kern<<<blocks, i.nt, shm, s>>>(
         d.X, d.ldx, d.n, d.p, d.y, d.tVc, d.tVr, d.a, d.d, d.Gf, d.cvec, d.ortho, x_lds, c.beta,
         c.u, c.lam, c.shape, c.sc, d.hy, d.betaburn, Key{r.k0, r.k1}, r.t0, r.count, r.first_slot,
@@ -934,9 +474,15 @@ void tri_launch(const TriChainsInstance &i, int blocks, hipStream_t s, const Cha
 
 }  // namespace
 
+// d.hy.know_alpha == 0 (engines and batches created under bb_set_tuning key 27): the instances
+// of bb_tri_mh.hip, which sample alpha in the sweep.
 void launch_tri_chain(hipStream_t s, const ChainDesign &d, const ChainState &c,
                       const ChainTraces &tr, const ChainRun &r) {
     if (r.count <= 0 || d.p < 1 || d.p > kTriChainMaxP) return;  // the engine checks p at setup
+    if (!d.hy.know_alpha) {
+        (void)tri_mh_launch(0, kTcNT, 1, s, d, c, tr, r);  // the 512-thread instance exists
+        return;
+    }
     static const hipError_t attr = hipFuncSetAttribute(  // one-time opt-in above 64 KB
         (const void *)k_tri_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTcXLds);
     (void)attr;
@@ -948,6 +494,7 @@ int launch_tri_chains(hipStream_t s, int nchains, int threads, const ChainDesign
     const TriChainsInstance *inst = tri_chains_instance(threads);
     if (!inst || d.p < 1 || d.p > kTriChainMaxP) return -1;  // the batch checks both at creation
     if (r.count <= 0 || nchains <= 0) return 0;
+    if (!d.hy.know_alpha) return tri_mh_launch(1, threads, nchains, s, d, c, tr, r);
     tri_launch(*inst, nchains, s, d, c, tr, r);
     return 0;
 }
@@ -956,10 +503,10 @@ int launch_tri_chains(hipStream_t s, int nchains, int threads, const ChainDesign
 // that holds every chain at once (a wider workgroup leaves wave 0 more of its SIMD), else the
 // one that holds the most.  Every instance gives the same bits, so this is a matter of speed
 // alone.
-int tri_chains_threads(int n, int p, int nchains, int cus) {
+int tri_chains_threads(int n, int p, int nchains, int cus, int mh) {
     int best = kTcNT, best_r = 0;
     for (int nt : {kTcNT, 256, 128}) {
-        const int r = tri_chains_resident_per_cu(n, p, nt);
+        const int r = tri_chains_resident_per_cu(n, p, nt, mh);
         if (r <= best_r) continue;
         best = nt;
         best_r = r;
@@ -968,13 +515,15 @@ int tri_chains_threads(int n, int p, int nchains, int cus) {
     return best;
 }
 
-int tri_chains_resident_per_cu(int n, int p, int threads) {
+int tri_chains_resident_per_cu(int n, int p, int threads, int mh) {
     const TriChainsInstance *inst = tri_chains_instance(threads);
     if (!inst) return -1;
+    // the kernel that will run: the MH instances have their own registers and LDS
+    const void *kern = mh ? tri_mh_batch_kernel(threads) : (const void *)inst->kern;
     int x_lds = 0, blocks = 0;
-    const size_t shm = tri_chains_shm(*inst, n, p, &x_lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)inst->kern, inst->nt,
-                                                     shm) != hipSuccess) {
+    const size_t shm = tri_chain_shm(inst->compact, n, p, &x_lds);
+    if (!kern ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kern, inst->nt, shm) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }

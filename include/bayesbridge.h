@@ -287,7 +287,10 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
  *
  * The triangle mixture (cfg->method == 4; bb_tri.hip k_tri_chains) runs as a batch wherever a
  * single engine runs k_tri_chain fused: p <= 32, p <= n, world == 1, alpha known, either
- * `ortho` value, any `betaburn`.  The SVD basis (or the Gram, for the orthogonal design) is
+ * `ortho` value, any `betaburn`; with bb_set_tuning key 27 set when the batch is created, alpha
+ * may be unknown (true_alpha <= 0): each chain samples its alpha inside the launch
+ * (k_tri_chains_mh, the same three instances), under the prior (alpha_a, alpha_b), and is bit
+ * for bit the chain of a bb_engine created under the key.  The SVD basis (or the Gram, for the orthogonal design) is
  * computed once for the batch.  omega is the batch's `lambda`; u and shape have the calls
  * bb_chains_get_tri_trace, bb_chains_set_tri_state and bb_chains_get_tri_basis, which mean for
  * chain `chain` what the bb_engine_* calls of those names mean.  A batch of more chains than
@@ -637,6 +640,20 @@ void bb_set_trace_budget(long long bytes);
  * one setting, chain c of a batch is bit for bit the c-th of sequential single-chain calls.
  * The triangle mixture, 32 < p <= 128 (key 25 or not), sharded, sparse and logistic engines are
  * as they are without the key.
+ * key 27 (alpha sampled in the fused triangle chains): triangle-mixture engines and chain batches
+ * created from now on with p <= 32, p <= n and alpha unknown (true_alpha <= 0) -- general or
+ * orthogonal design, any betaburn, world == 1 -- run whole sweeps, the alpha Metropolis-Hastings
+ * step included, in one workgroup (bb_tri_mh.hip: k_tri_chain_mh for bb_engine, bridge_regression
+ * and every single-chain call; k_tri_chains_mh, a workgroup of 512, 256 or 128 threads per chain
+ * as k_tri_chains, for bb_chains_create and the *_chains calls, which otherwise refuse alpha
+ * unknown or run the chains one after another) (1), or the general path (0, the default).  What
+ * exists keeps the path it was created with.  The fused chain uses the general path's counters
+ * and the prior pair (alpha_a, alpha_b) of both phases; it sums S_alpha and the two sums of the
+ * MH step in another order than the general path, so it is not bit for bit that path's chain,
+ * hence opt-in (and not key 26: a method-4 batch with alpha unknown stays refused under keys 25
+ * and 26).  Under one setting, chain c of a batch is bit for bit the c-th of sequential
+ * single-chain calls, with every instance.  p > 32, p > n and sharded triangle engines are as
+ * they are without the key.
  * A negative value changes nothing.  Returns the previous value, or -1 for an unknown key. */
 int bb_set_tuning(int key, int value);
 /* Test hook: the k-th interrupt poll from now reports an interrupt (k >= 0; -1 clears). */

@@ -29,6 +29,9 @@ known-alpha batch, each as the call and kernel only.  The baseline a batch has t
 bridge_reg_stb_chains(alpha = 0) without the key, K sequential general-path chains:
 --alpha --mode single [--tree DIR] measures it (on the parent checkout, say; fewer samples keep
 K = 1024 sequential chains affordable) as one JSON line, which --baseline FILE merges.
+--alpha --method tri is the same for the triangle mixture under key 27 (bb_tri_mh.hip:
+k_tri_chain_mh, k_tri_chains_mh against k_tri_chains) into profiles/chains_tri_alpha_{c1,db}.json,
+with the threads of the instance each K ran.
 
 --wide measures the wide fused chains (bb_set_tuning key 25, bb_wide.hip) at the published
 protocol's wider shapes, synthetic designs dbi (442 x 64) and bhi (506 x 103), into
@@ -60,6 +63,7 @@ median over rounds is reported with the min and max beside it.
   python tools/bench_chains.py --wide [--designs dbi]
   python tools/bench_chains.py --alpha --mode single --tree DIR --nsamp 100 --burn 50 > FILE
   python tools/bench_chains.py --alpha --baseline FILE
+  python tools/bench_chains.py --alpha --method tri [--mode single --tree DIR | --baseline FILE]
   python tools/bench_chains.py --logit --mode single --tree DIR > FILE
   python tools/bench_chains.py --logit --baseline FILE
 """
@@ -144,14 +148,17 @@ def spread(v):
     return {"median": float(np.median(v)), "min": float(v[0]), "max": float(v[-1])}
 
 
-def kernel_rate(me, X, y, K, nsamp, threads=0, block=50, true_alpha=0.5):
+def kernel_rate(me, X, y, K, nsamp, threads=0, block=50, true_alpha=0.5, ran=None):
     """Sweeps/s of the batch kernel alone: blocks of `block` sweeps, no traces, one sync.
-    threads: the triangle batch's instance (0: the one the batch selects)."""
+    threads: the triangle batch's instance (0: the one the batch selects); ran: a dict that
+    receives the threads per workgroup of the instance that ran, under K."""
     n, p = X.shape
     b = me.bb.ChainBatch(me.config(n, p, true_alpha=true_alpha), K, X, y)
     try:
         if threads:
             b.set_threads(threads)
+        if ran is not None:
+            ran[K] = b.threads()
         b.init_state()
         b.run(1, 500, 0, 0, 0)
         b.sync()
@@ -362,24 +369,41 @@ def bench_wide(me, name, X, y, cus, args):
             "chains": rows, "kernels": kernels}
 
 
-ALPHA_KEY = 26  # bb_set_tuning: alpha sampled in the fused small chains (bb_small_mh.hip)
+# bb_set_tuning: alpha sampled in the fused small chains (bb_small_mh.hip) and in the fused
+# triangle chains (bb_tri_mh.hip)
+ALPHA_KEY, TRI_ALPHA_KEY = 26, 27
+
+
+def alpha_kernels(me, p, threads):
+    """The kernels a --alpha run launches: the single chain's and the batch's alpha-sampling
+    instances and the known-alpha batch's; threads: the triangle batch instances it ran."""
+    if me.tri:
+        inst = sorted({f"{t}, {'false' if t == 512 else 'true'}" for t in threads})
+        anon = "bb::(anonymous namespace)::"
+        return ([anon + "k_tri_chain_mh"] + [anon + f"k_tri_chains_mh<{i}>" for i in inst]
+                + [anon + f"k_tri_chains<{i}>" for i in inst])
+    lanes = "512, 64, 16" if p <= 8 else "512, 32, 8" if p <= 16 else "512, 16, 8"
+    return [f"bb::k_small_chain_mh<{lanes}>", f"bb::k_small_chains_mh<{lanes}>",
+            f"bb::k_small_chains<{lanes}>"]
 
 
 def bench_alpha(me, name, X, y, cus, args):
-    """Alpha unknown (alpha = 0: sampled by MH) under key 26 against this tree's known-alpha
-    batch, alternated within each round; the key is set only around the calls it is measured in
-    and left off.  The sequential general-path fallback at the same K comes from --baseline."""
+    """Alpha unknown (alpha = 0: sampled by MH) under key 26 (--method tri: key 27) against this
+    tree's known-alpha batch, alternated within each round; the key is set only around the calls
+    it is measured in and left off.  The sequential general-path fallback at the same K comes
+    from --baseline."""
     bb = me.bb
+    key = TRI_ALPHA_KEY if me.tri else ALPHA_KEY
     Ks = [k for k in (args.chains or [1, 256, 1024]) if k <= args.max_chains]
     nsamp, burn = args.nsamp, args.burn
 
     def call(on, fn):
-        old = bb.set_tuning(ALPHA_KEY, 1 if on else 0)
+        old = bb.set_tuning(key, 1 if on else 0)
         try:
             bb.set_seed(SEED)
             return fn()
         finally:
-            bb.set_tuning(ALPHA_KEY, old)
+            bb.set_tuning(key, old)
 
     call(1, lambda: me.chains(y, X, nsamp=200, nchains=2, burn=100, alpha=0.0))  # warm-up
     call(1, lambda: me.single(y, X, nsamp=200, burn=100, alpha=0.0))
@@ -387,7 +411,7 @@ def bench_alpha(me, name, X, y, cus, args):
     call(0, lambda: me.chains(y, X, nsamp=200, nchains=2, burn=100))
     keys = ("mh", "mh_kernel", "known", "known_kernel")
     v = {K: {k: [] for k in keys} for K in Ks}
-    one_fused, one_general, res = [], [], {}
+    one_fused, one_general, res, ran = [], [], {}, {}
     for _ in range(args.reps):
         one_fused.append(nsamp / call(1, lambda: me.single(y, X, nsamp=nsamp, burn=burn,
                                                            alpha=0.0))["runtime"])
@@ -397,7 +421,8 @@ def bench_alpha(me, name, X, y, cus, args):
             out = call(1, lambda: me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn, alpha=0.0))
             v[K]["mh"].append(K * nsamp / out["runtime"])
             del out
-            kr, res[K] = call(1, lambda: kernel_rate(me, X, y, K, nsamp, true_alpha=0.0))
+            kr, res[K] = call(1, lambda: kernel_rate(me, X, y, K, nsamp, true_alpha=0.0,
+                                                     ran=ran))
             v[K]["mh_kernel"].append(kr)
             out = call(0, lambda: me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn))
             v[K]["known"].append(K * nsamp / out["runtime"])
@@ -414,7 +439,7 @@ def bench_alpha(me, name, X, y, cus, args):
     rows = []
     for K in Ks:
         s = {k: spread(v[K][k]) for k in keys}
-        row = {"chains": K, "resident_per_cu": res[K],
+        row = {"chains": K, "resident_per_cu": res[K], "threads": ran[K],
                "alpha_sampled_call_sweeps_per_s": s["mh"],
                "alpha_sampled_kernel_sweeps_per_s": s["mh_kernel"],
                "alpha_known_call_sweeps_per_s": s["known"],
@@ -429,13 +454,12 @@ def bench_alpha(me, name, X, y, cus, args):
         rows.append(row)
     from bayesbridge_amd import _kernel_code
 
-    lanes = "512, 64, 16" if X.shape[1] <= 8 else "512, 32, 8" if X.shape[1] <= 16 else "512, 16, 8"
     kernels = {k: {"code_sha": _kernel_code.code_sha(k)}
-               for k in (f"bb::k_small_chain_mh<{lanes}>", f"bb::k_small_chains_mh<{lanes}>",
-                         f"bb::k_small_chains<{lanes}>")}
+               for k in alpha_kernels(me, X.shape[1], ran.values())}
     f1, g1 = spread(one_fused), spread(one_general)
     rec = {"design": name, "n": int(X.shape[0]), "p": int(X.shape[1]), "nsamp": nsamp,
            "burn": burn, "reps": args.reps, "compute_units": cus,
+           "method": "tri" if me.tri else "stable", "tuning_key": key,
            "single_call_fused_sweeps_per_s": f1, "single_call_general_path_sweeps_per_s": g1,
            "single_fused_vs_general_path": f1["median"] / g1["median"],
            "chains": rows, "kernels": kernels}
@@ -445,9 +469,9 @@ def bench_alpha(me, name, X, y, cus, args):
 
 
 def bench_alpha_fallback(me, args):
-    """bridge_reg_stb_chains(alpha = 0) with every key as the checkout has it (one JSON line):
-    on a checkout without key 26, or with it off, K sequential general-path chains -- the
-    baseline of --alpha, through --baseline."""
+    """bridge_reg_stb_chains(alpha = 0) (--method tri: bridge_reg_tri_chains) with every key as
+    the checkout has it (one JSON line): on a checkout without key 26 (27), or with it off, K
+    sequential general-path chains -- the baseline of --alpha, through --baseline."""
     out = {}
     for name, (X, y) in designs().items():
         if name not in args.designs.split(","):
@@ -464,8 +488,8 @@ def bench_alpha_fallback(me, args):
                 del r
             out[name][str(K)] = spread(v)
             print(f"{name} K={K:5d} fallback {out[name][str(K)]}", file=sys.stderr, flush=True)
-    print(json.dumps({"source_sha": me.bb._build.source_sha(), "nsamp": args.nsamp,
-                      "burn": args.burn, "reps": args.reps,
+    print(json.dumps({"source_sha": me.bb._build.source_sha(), "method": args.method,
+                      "nsamp": args.nsamp, "burn": args.burn, "reps": args.reps,
                       "fallback_chains_sweeps_per_s": out}), flush=True)
 
 
@@ -614,7 +638,8 @@ def main():
     ap.add_argument("--wide", action="store_true",
                     help="the wide fused chains (key 25) at dbi / bhi (profiles/chains_wide_*)")
     ap.add_argument("--alpha", action="store_true",
-                    help="alpha unknown under key 26 (profiles/chains_alpha_*)")
+                    help="alpha unknown under key 26 (profiles/chains_alpha_*); --method tri: "
+                         "under key 27 (profiles/chains_tri_alpha_*)")
     ap.add_argument("--logit", action="store_true",
                     help="the logistic chain batch at lg5 / lg32 (profiles/chains_logit_*)")
     ap.add_argument("--baseline", default=None,
@@ -667,7 +692,8 @@ def main():
         if args.alpha:
             rec = bench_alpha(me, name, X, y, cus, args)
             rec["source_sha"] = bb._build.source_sha()
-            with open(os.path.join(args.out_dir, f"chains_alpha_{name}{args.tag}.json"), "w") as f:
+            stem = "chains_tri_alpha_" if me.tri else "chains_alpha_"
+            with open(os.path.join(args.out_dir, f"{stem}{name}{args.tag}.json"), "w") as f:
                 json.dump(rec, f, indent=1)
                 f.write("\n")
             f1, g1 = rec["single_call_fused_sweeps_per_s"], rec["single_call_general_path_sweeps_per_s"]

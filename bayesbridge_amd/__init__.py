@@ -78,7 +78,7 @@ EXPORTED_SYMBOLS = [
     "bb_chains_set_threads", "bb_compute_units", "bridge_reg_stable_chains_summary",
     "bridge_regression_chains_summary", "bb_chains_summary_reset", "bb_chains_summary_add",
     "bb_chains_summary_get", "bb_trace_summary", "bridge_reg_logit_chains",
-    "bridge_reg_logit_chains_summary", "bb_chains_get_omega",
+    "bridge_reg_logit_chains_summary", "bb_chains_get_omega", "bb_set_em_scratch_budget",
 ]
 
 
@@ -142,6 +142,7 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_set_chol_version.argtypes = [c.c_int]
     L.bb_set_tuning.argtypes = [c.c_int, c.c_int]
     L.bb_set_trace_budget.argtypes = [c.c_longlong]
+    L.bb_set_em_scratch_budget.argtypes = [c.c_longlong]
     L.bb_debug_interrupt_after.argtypes = [c.c_int]
     L.bb_last_call_info.argtypes = [_ip, _ip, _ip]
     L.bb_debug_fail_member.argtypes = [c.c_int, c.c_int]
@@ -349,6 +350,12 @@ def chol_version() -> int:
 def set_trace_budget(nbytes: int) -> None:
     """Device bytes of the trace ring per engine (<= 0 restores the 1 GiB default)."""
     library().bb_set_trace_budget(int(nbytes))
+
+
+def set_em_scratch_budget(nbytes: int) -> None:
+    """Test hook: cap the scratch of one chunk of ratios in bridge_em_batch above p = 128
+    (<= 0 restores the default, min(free / 2, 16 GiB) alone)."""
+    library().bb_set_em_scratch_budget(int(nbytes))
 
 
 def debug_interrupt_after(polls: int) -> None:

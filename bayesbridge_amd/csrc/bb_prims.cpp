@@ -582,6 +582,14 @@ int bb_bridge_em(double *beta_out, const double *yh, const double *Xh, int n, in
     return ret;
 }
 
+// Test hook (bb_set_em_scratch_budget): a further cap, in bytes, on the scratch of one chunk of
+// ratios in bb_bridge_em_batch, so that tests reach its chunk loop; 0 = no further cap.
+static size_t g_em_scratch_budget = 0;
+
+void bb_set_em_scratch_budget(long long bytes) {
+    g_em_scratch_budget = bytes > 0 ? (size_t)bytes : 0;
+}
+
 // Batched EM over `count` ratios (trace.beta), direct solves: X'X and X'y once, then one
 // launch in which a workgroup per ratio runs the whole EM -- k_em_batch (system in LDS) for
 // p <= 128, k_em_batch_tiled (system in a global scratch slice per ratio, tiled Cholesky)
@@ -630,7 +638,8 @@ int bb_bridge_em_batch(double *beta, int *solves, const double *yh, const double
             const size_t per = (size_t)pe * pe * sizeof(double);
             size_t fr = 0, tot = 0;
             HIPCHECK(hipMemGetInfo(&fr, &tot));
-            const size_t budget = std::min(fr / 2, (size_t)16 << 30);
+            size_t budget = std::min(fr / 2, (size_t)16 << 30);
+            if (g_em_scratch_budget) budget = std::min(budget, g_em_scratch_budget);
             const int chunk = (int)std::max<size_t>(1, std::min<size_t>(count, budget / per));
             if (per > fr) throw HipError("bb_bridge_em_batch: p x p system does not fit");
             double *scr = dev.alloc<double>((size_t)chunk * pe * pe);

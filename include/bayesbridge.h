@@ -832,6 +832,10 @@ int bb_bridge_em(double *beta, const double *y, const double *X, int n, int p, d
 int bb_bridge_em_batch(double *beta, int *solves, const double *y, const double *X, int n,
                        int p, const double *ratios, const double *lambda_max, int count,
                        double alpha, double tol, int max_iter);
+/* Test hook: a further cap, in bytes, on the scratch of one chunk of ratios of
+ * bb_bridge_em_batch above p = 128 (a ratio takes round_up(p, 64)^2 doubles; a chunk is never
+ * smaller than one ratio).  0 restores the default, min(free / 2, 16 GiB) alone. */
+void bb_set_em_scratch_budget(long long bytes);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,7 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_kernel_instance.argtypes = [c.c_char_p, c.c_char_p, c.c_int]
     L.bb_engine_nid_mixed.argtypes = [c.c_void_p, u64p, u64p, _dp, _ip, _ip]
     L.bb_engine_nid_beta32.argtypes = [c.c_void_p, u64p, _ip]
+    L.bb_engine_nid_resid.argtypes = [c.c_void_p, u64p, u64p, _dp]
     L.bb_group_destroy.argtypes = [c.c_void_p]
     L.bb_group_init_state.argtypes = [c.c_void_p]
     L.bb_group_run.argtypes = [c.c_void_p, c.c_uint64, c.c_int, c.c_int, c.c_int, c.c_int]
@@ -1490,7 +1491,15 @@ class Engine:
         library().bb_engine_nid_bound(self._h, ctypes.byref(lam), ctypes.byref(kmax))
         return dict(cheb_sweeps=a.value, products=b.value, chol_sweeps=c.value, eps=eps.value,
                     mode=mode.value, lambda_x=lam.value, kmax=kmax.value,
-                    beta32_sweeps=self._beta32()[0])
+                    beta32_sweeps=self._beta32()[0], redo_sweeps=self._resid()[1])
+
+    def _resid(self):
+        """(sweeps whose correction the fp64 residual chose; sweeps redone on the
+        a-priori plan; the latest certificate's ratio)"""
+        a, b, r = ctypes.c_ulonglong(), ctypes.c_ulonglong(), ctypes.c_double()
+        _check(library().bb_engine_nid_resid(self._h, ctypes.byref(a), ctypes.byref(b),
+                                             ctypes.byref(r)), "bb_engine_nid_resid")
+        return a.value, b.value, r.value
 
     def _beta32(self):
         """(sweeps that took the fp32 beta pass; whether the latest did)"""
@@ -1502,15 +1511,19 @@ class Engine:
     def nid_mixed(self):
         """The mixed-precision plan: dict(mixed_sweeps, products32 (fp32
         E-apply passes), eta and k2 of the latest sweep, holds_x32, beta32_sweeps and
-        beta32: sweeps that took the fp32 beta pass of s6.7, whether the latest did)."""
+        beta32: sweeps that took the fp32 beta pass of s6.7, whether the latest did;
+        resid_sweeps, redo_sweeps and resid_ratio: sweeps whose correction the fp64 residual
+        chose (s6.8), sweeps redone on the a-priori plan, the latest certificate's ratio)."""
         a, b = ctypes.c_ulonglong(), ctypes.c_ulonglong()
         eta, k2, hx = ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
         _check(library().bb_engine_nid_mixed(self._h, ctypes.byref(a), ctypes.byref(b),
                                              ctypes.byref(eta), ctypes.byref(k2),
                                              ctypes.byref(hx)), "bb_engine_nid_mixed")
         n32, last32 = self._beta32()
+        nres, nredo, ratio = self._resid()
         return dict(mixed_sweeps=a.value, products32=b.value, eta=eta.value, k2=k2.value,
-                    holds_x32=bool(hx.value), beta32_sweeps=n32, beta32=last32)
+                    holds_x32=bool(hx.value), beta32_sweeps=n32, beta32=last32,
+                    resid_sweeps=nres, redo_sweeps=nredo, resid_ratio=ratio)
 
     def launch_counts(self):
         """Woodbury lambda launches since creation: dict(lambda_xu = fused with the X u stream

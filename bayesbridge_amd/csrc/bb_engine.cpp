@@ -121,6 +121,13 @@ int g_nid_fold = 1;
 // 1 where certified and the cost model says the halved pass pays (the default), 2 wherever
 // certified (tests at small shapes)
 int g_nid_b32 = 1;
+// bb_set_tuning key 29: the residual-certified mixed plan (unsharded dense engines
+// holding X32 that decide under the synchronous protocol with the polled tag): the first solve
+// on a guessed interval, K2 from the fp64 residual.  0 never (the plan search of s6.6 / s6.7 bit
+// for bit), 1 where the cost model says an fp32 pass is worth several launches (the default),
+// 2 wherever a first solve qualifies (tests at small shapes), 2 + v the same with the guess
+// factor phi = 8 / 16^v (tests: a wrong guess, the redo)
+int g_nid_resid = 1;
 // bb_set_tuning key 21: chain batches of at least 2 x CUs chains created from now on run the
 // 256-thread instance, two chains per CU (faster in aggregate there; its chains
 // match the oracle but are not bit for bit those of sequential calls)
@@ -217,6 +224,12 @@ struct bb_engine {
     // decision set NidState::b32
     double *gb = nullptr, *ch_c = nullptr, *ch_xu = nullptr;
     bool nid_b32 = false;
+    // the residual-certified plan: the partials of |b|^2 and |r|^2 (nid_sqn of
+    // each), whether the latest decision took it, and the second decisions launched with a tag
+    double *nid_sq = nullptr;
+    int nid_sqn = 0;
+    bool nid_resid = false;
+    unsigned long long nid_kseq = 0;
     double nid_cost[3] = {0.0, 0.0, 0.0};  // NidState c64, c32, cstep (s)
     int ea_parts = 1;
     int nid_kmax = 0;  // iterations beyond which the Gram + Cholesky path is cheaper (model)
@@ -326,9 +339,20 @@ struct bb_engine {
     // keeps b), decides under the synchronous protocol (the host learns the flag with the
     // decision) and has the fused beta pass's shape
     bool b32_ok() const { return gb != nullptr && g_nid_b32 && mixed_ok() && nid_sync(); }
+    // the decision may take the residual-certified plan: a mixed-plan engine whose host polls
+    // the decision tags; by default only where an fp32 pass costs more than four step launches
+    // (the plan adds a launch and a second host wake-up to save such passes: C3's shape, not
+    // the 2048 x 6250 and smaller designs whose tests pin the a-priori plan and its beta32 rule)
+    bool resid_ok() const {
+        return nid_sq != nullptr && g_nid_resid && g_nid_poll && mixed_ok() && nid_sync() &&
+               (g_nid_resid >= 2 || nid_cost[1] > 4.0 * nid_cost[2]);
+    }
     int allow_mask() const {
         return (mixed_ok() ? kAllowMixed : 0) |
-               (b32_ok() ? kAllowBeta32 | (g_nid_b32 == 2 ? kBeta32AnyCost : 0) : 0);
+               (b32_ok() ? kAllowBeta32 | (g_nid_b32 == 2 ? kBeta32AnyCost : 0) : 0) |
+               (resid_ok() ? kAllowResid | (g_nid_resid >= 2 ? kResidAnyCost : 0) |
+                                 (std::max(g_nid_resid - 2, 0) << kResidPhiShift)
+                           : 0);
     }
     double *bank() const { return b32_ok() ? gb : nullptr; }
     Beta32Vecs b32_vecs() const {
@@ -458,9 +482,11 @@ struct bb_engine {
         int mode, k2;
         if (g_nid_poll) {
             const unsigned long long tag = wait_tag(nid_dseq);
-            mode = (int)((tag >> 8) & 0xff);
+            mode = (int)((tag >> 8) & 0x7f);
+            nid_resid = ((tag >> 15) & 1) != 0;  // mode <= 64: resid rides in its bit 7
             k2 = (int)(tag & 0xff);
         } else {
+            nid_resid = false;
             wait_event(nid_sev);
             mode = (int)((volatile double *)eps_host)[kNidRing + 1];
             k2 = (int)((volatile double *)eps_host)[kNidRing + 2];
@@ -477,12 +503,13 @@ struct bb_engine {
     // 1024 polls the stream is queried: a device error surfaces as the HIP error, and a drained
     // stream without the tag is an error (never a silent wrong path); a shard-group member
     // gives up when another member failed (wait_event).
-    unsigned long long wait_tag(unsigned long long seq) {
-        const unsigned long long *tp = (const unsigned long long *)(eps_host + kNidRing + 3);
-        const unsigned long long want = seq & 0xffffffffffffull;
+    // slot 4 / shift 24: the residual-certified plan's second decision (k_nid_k2)
+    unsigned long long wait_tag(unsigned long long seq, int slot = 3, int shift = 16) {
+        const unsigned long long *tp = (const unsigned long long *)(eps_host + kNidRing + slot);
+        const unsigned long long want = seq & (~0ull >> shift);
         for (long spin = 0;; ++spin) {
             const unsigned long long v = __atomic_load_n(tp, __ATOMIC_ACQUIRE);
-            if ((v >> 16) == want) return v;
+            if ((v >> shift) == want) return v;
             if ((spin & 1023) != 1023) {
                 __builtin_ia32_pause();
                 continue;
@@ -492,7 +519,7 @@ struct bb_engine {
             const hipError_t q = hipStreamQuery(stream);
             if (q == hipSuccess) {
                 const unsigned long long w = __atomic_load_n(tp, __ATOMIC_ACQUIRE);
-                if ((w >> 16) == want) return w;
+                if ((w >> shift) == want) return w;
                 throw HipError("near-identity decision tag not written by the drained stream");
             }
             if (q != hipErrorNotReady) HIPCHECK(q);
@@ -536,11 +563,13 @@ struct bb_engine {
         else
             launch_cheb_init(stream, nid_xu, xu_fused ? xu_fused : ea_parts, n, n_pad, y, sc,
                              cfg.seed, cfg.stream, t, nid, w, ch_r, ch_d,
-                             mixed_ok() ? ch_b : nullptr, b32_ok() ? ch_xu : nullptr);
+                             mixed_ok() ? ch_b : nullptr, b32_ok() ? ch_xu : nullptr,
+                             resid_ok() ? nid_sq : nullptr);
     }
     // the mixed plan's residual pass, restart and correction solve (k2 iterates), after the
     // first solve's products
     void nidx_mixed_tail(int k2) {
+        if (nid_resid) return nidx_resid_tail();
         const Beta32Vecs bv = b32_vecs();
         mark(PH_EAPPLY);
         launch_eapply(stream, X, n_pad, n_pad, p_loc, D, w, nid, 0, ea_part, X32, 2, bank());
@@ -553,6 +582,48 @@ struct bb_engine {
             launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d, 2,
                              &bv);
         }
+    }
+    // The same tail on a residual-certified sweep: the residual pass, the
+    // restart and the second decision, then -- before the host waits for that decision -- the
+    // correction's first product and step (they return at once unless the device's K2 >= 2, as
+    // the speculative first product of solve_schedule does); after it the remaining K2 - 2
+    // products, or the redo: the sweep's a-priori plan from x = 0 and the stored b.
+    void nidx_resid_tail() {
+        const Beta32Vecs bv = b32_vecs();
+        const int gb_ = cheb_sq_parts(n_pad, xu_fused ? xu_fused : ea_parts);
+        const int gr_ = cheb_sq_parts(n_pad, ea_parts);
+        mark(PH_EAPPLY);
+        launch_eapply(stream, X, n_pad, n_pad, p_loc, D, w, nid, 0, ea_part, X32, 2, bank());
+        mark(PH_NID);
+        launch_cheb_restart(stream, ea_part, ea_parts, n_pad, sc, nid, ch_b, w, ch_r, ch_d, &bv,
+                            nid_sq + nid_sqn);
+        launch_nid_k2(stream, nid_sq, gb_, nid_sq + nid_sqn, gr_, std::min(g_nid_kmax, nid_kmax),
+                      sc, nid, &bv, w, n_pad,
+                      (unsigned long long *)(eps_dev + kNidRing + 4), ++nid_kseq);
+        auto correction = [&](int j) {
+            mark(PH_EAPPLY);
+            launch_eapply(stream, X, n_pad, n_pad, p_loc, D, ch_d, nid, j, ea_part, X32, 3);
+            mark(PH_NID);
+            launch_cheb_step(stream, ea_part, ea_parts, n_pad, sc, nid, j, w, ch_r, ch_d, 2,
+                             &bv);
+        };
+        correction(1);
+        const unsigned long long tag = wait_tag(nid_kseq, 4, 24);
+        const int mode = (int)((tag >> 8) & 0xff), k2 = (int)(tag & 0x7f);
+        nid_b32 = b32_ok() && (tag & 128) != 0;
+        nid_k2 = k2;
+        nid_last = mode;
+        nid_resid = false;
+        if (((tag >> 16) & 1) == 0) {
+            for (int j = 2; j < k2; ++j) correction(j);
+            return;
+        }
+        launch_nid_redo(stream, nid, ch_b, n_pad, w, ch_r, ch_d);
+        for (int j = 1; j < mode; ++j) {
+            nidx_eapply(j);
+            nidx_step(j);
+        }
+        if (k2 > 0) nidx_mixed_tail(k2);
     }
     // this shard's E d of step j into nid_sum (exchanged: n_pad)
     void nidx_eapply(int j) {
@@ -1214,6 +1285,15 @@ void nid_certify_lambda(bb_engine *e) {
     HIPCHECK(hipMemcpyAsync(&e->nid->lambda_x, &lam, sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(&e->nid->c64, e->nid_cost, sizeof(e->nid_cost), hipMemcpyHostToDevice,
                             s));
+    // sum_j |x_j|^2 for the guessed interval of the residual-certified plan,
+    // added on the host in column order
+    std::vector<double> hcn(e->p_loc);
+    HIPCHECK(hipMemcpyAsync(hcn.data(), e->cn, hcn.size() * sizeof(double), hipMemcpyDeviceToHost,
+                            s));
+    HIPCHECK(hipStreamSynchronize(s));
+    double scn = 0.0;
+    for (double v : hcn) scn += v;
+    HIPCHECK(hipMemcpyAsync(&e->nid->sum_cn, &scn, sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHECK(hipStreamSynchronize(s));
     e->lambda_x = lam;
     (void)hipFree(ones);
@@ -1364,11 +1444,12 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
             e->nid_sum = dalloc<double>(n_pad, o);
             // the hint ring, then [eps, mode, k2, tag] of the sweep being decided (coherent:
             // the host polls the tag while the device runs on)
-            const int nh = bb_engine::kNidRing + 4;
+            const int nh = bb_engine::kNidRing + 5;  // + the second decision's tag (s6.8)
             HIPCHECK(hipHostMalloc((void **)&e->eps_host, nh * sizeof(double),
                                    hipHostMallocMapped | hipHostMallocCoherent));
             for (int q = 0; q < nh; ++q) e->eps_host[q] = -1.0;  // no observation yet
             *(unsigned long long *)(e->eps_host + bb_engine::kNidRing + 3) = 0ull;
+            *(unsigned long long *)(e->eps_host + bb_engine::kNidRing + 4) = 0ull;
             HIPCHECK(hipHostGetDevicePointer((void **)&e->eps_dev, e->eps_host, 0));
             e->nid_kmax = e->nid_kmax_model();
             // the mixed-precision plan's fp32 copy of X (unsharded dense engines; 4 B per
@@ -1394,6 +1475,11 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
                     } else {
                         o.push_back(x32);
                         e->X32 = (float *)x32;
+                        // the residual certificate's partials of |b|^2 and |r|^2
+                        e->nid_sqn = (n_pad + 7) / 8;
+                        e->nid_sq = dalloc<double>(2 * (size_t)e->nid_sqn, o);
+                        HIPCHECK(hipMemsetAsync(e->nid_sq, 0, 2 * sizeof(double) * e->nid_sqn,
+                                                e->stream));
                         if (beta_xb_supported(n_pad)) {  // the fp32 beta pass's vectors
                             e->gb = dalloc<double>(p_pad, o);
                             e->ch_c = dalloc<double>(n_pad, o);
@@ -2216,6 +2302,20 @@ int bb_engine_nid_beta32(bb_engine *e, unsigned long long *beta32_sweeps, int *b
         }
         if (beta32_sweeps) *beta32_sweeps = h.n_beta32;
         if (b32) *b32 = h.b32;
+    });
+}
+
+int bb_engine_nid_resid(bb_engine *e, unsigned long long *resid_sweeps,
+                        unsigned long long *redo_sweeps, double *ratio) {
+    return guarded([&] {
+        NidState h{};
+        if (e->nid) {
+            HIPCHECK(hipMemcpyAsync(&h, e->nid, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(hipStreamSynchronize(e->stream));
+        }
+        if (resid_sweeps) *resid_sweeps = h.n_resid;
+        if (redo_sweeps) *redo_sweeps = h.n_redo;
+        if (ratio) *ratio = h.ratio;
     });
 }
 
@@ -3522,7 +3622,7 @@ int bb_set_tuning(int key, int value) {
                  {12, &g_rs_xcd, 1},    {13, &g_lam_wave, 1},  {15, &g_lam_lend, 1},
                  {17, &g_nid_fold, 2},  {20, &g_bsolve_ll, 1}, {21, &g_chains_packed, 1},
                  {24, &g_nid_b32, 2},   {25, &g_chains_wide, 1}, {26, &g_fused_alpha, 1},
-                 {27, &g_fused_tri_alpha, 1}};
+                 {27, &g_fused_tri_alpha, 1}, {29, &g_nid_resid, 8}};
     for (const auto &k : kKeys)
         if (k.key == key) {
             const int old = *k.var;

@@ -63,6 +63,17 @@ struct NidState {
     // in place of k_beta_wb_xb); n_beta32 counts such sweeps
     int b32;
     unsigned long long n_beta32;
+    // the residual-certified plan (bb_set_tuning key 29).  resid: this sweep's
+    // first solve runs mode iterates on the guessed interval [1, 1 + eps1] (theta / delta / sigma1
+    // are then eps1's), and k_nid_k2 replaces k2 and b32 -- provisional until then: the predicted
+    // K2 and "the banks are wanted" -- by what the fp64 residual certifies.  The correction solve
+    // always runs on the certified interval [1, 1 + e2] (theta2 / delta2 / sigma12; equal to
+    // theta / delta / sigma1 on every other sweep).  fb_*: the sweep's a-priori plan, adopted by
+    // k_nid_adopt when the residual certifies no K2 (a redo).  sum_cn = sum_j |x_j|^2 (setup);
+    // ratio: the latest certificate's |r| (1 + eps)(1 + 1e-6) / |b|.
+    int resid, fb_mode, fb_k2, fb_b32;
+    double theta2, delta2, sigma12, e2, fb_eta, sum_cn, ratio;
+    unsigned long long n_resid, n_redo;
 };
 constexpr double kNidTol = 1.3877787807814457e-17;  // 2^-56: bound on the relative error
 // 2^-26: the largest |w_s| / |w| at which the part w_s of w may be dotted against fl32(X) in
@@ -133,6 +144,10 @@ constexpr int kNidTS = 32;
 // the decision's allow_mixed mask: the mixed plan may be chosen; the sweep may take the fp32
 // beta pass (NidState::b32); ... whatever the cost model says (bb_set_tuning key 24 = 2)
 constexpr int kAllowMixed = 1, kAllowBeta32 = 2, kBeta32AnyCost = 4;
+// ... the residual-certified plan may be chosen (bb_set_tuning key 29);
+// kResidAnyCost: wherever a first solve qualifies, whatever the cost model says (key 29 >= 2);
+// bits 8..: the key's test value minus 2, which divides the guess factor phi = 8 by 16 per unit
+constexpr int kAllowResid = 8, kResidAnyCost = 16, kResidPhiShift = 8;
 int nid_sum_groups(int p_loc);
 void launch_nid_sums(hipStream_t s, const double *D, const double *cn, int p_loc,
                      const DevScalars *sc, NidState *nid, int k_launched, int allow, int decide,
@@ -171,7 +186,7 @@ void launch_nid_xu(hipStream_t s, const double *X, int ldx, const double *u, int
 void launch_cheb_init(hipStream_t s, const double *xu_part, int nparts, int n, int n_pad,
                       const double *y, const DevScalars *sc, uint64_t k0, uint64_t k1,
                       uint64_t t, const NidState *nid, double *x, double *r, double *d,
-                      double *b = nullptr, double *xu = nullptr);
+                      double *b = nullptr, double *xu = nullptr, double *sqb = nullptr);
 // The n-vectors of an engine that may take the fp32 beta pass.  The restart
 // writes the mixed plan's correction into c and its steps add to it (c = w - x0, accumulated,
 // not formed as a difference).  On a b32 sweep the solve's last step (or restart) writes
@@ -191,7 +206,23 @@ void launch_cheb_step(hipStream_t s, const double *part, int nparts, int n_pad,
 // d = r / theta, x += d (runs if k2 > 0 and mode > 0)
 void launch_cheb_restart(hipStream_t s, const double *part, int nparts, int n_pad,
                          const DevScalars *sc, const NidState *nid, const double *b, double *x,
-                         double *r, double *d, const Beta32Vecs *bv = nullptr);
+                         double *r, double *d, const Beta32Vecs *bv = nullptr,
+                         double *sqr = nullptr);
+// The residual-certified plan's second decision, after the restart: sqb / sqr =
+// the per-workgroup partials of sum b_i^2 (launch_cheb_init) and sum r_i^2 (launch_cheb_restart),
+// cheb_sq_parts(n_pad, nparts) of them (Gb, Gr).  One workgroup adds them in a fixed order, takes the
+// least K2 <= kcap the residual certifies, sets NidState::k2 and b32 (and, at K2 = 1 on a b32
+// sweep, writes the X beta the restart could not), or -- no K2 -- gates the sweep's remaining
+// launches off (mode = k2 = 0) for the redo.  tag (coherent host memory) receives
+// seq << 24 | redo << 16 | mode << 8 | b32 << 7 | k2 (a redo: the a-priori plan's).
+int cheb_sq_parts(int n_pad, int nparts);
+void launch_nid_k2(hipStream_t s, const double *sqb, int Gb, const double *sqr, int Gr, int kcap,
+                   const DevScalars *sc, NidState *nid, const Beta32Vecs *bv, const double *w,
+                   int n_pad, unsigned long long *tag, unsigned long long seq);
+// a redo: the a-priori plan into the live decision words, then x = d = b / theta, r = b (the
+// initial iterate again, from the stored right-hand side)
+void launch_nid_redo(hipStream_t s, NidState *nid, const double *b, int n_pad, double *x,
+                     double *r, double *d);
 // One pass over X: part = X D X' v partials.  kind 0: product j of the first solve (runs if
 // mode > j; streams X32 when the sweep took the mixed plan and X32 is given); 2: the mixed
 // plan's fp64 residual pass (v = the iterate; runs if k2 > 0 and mode > 0); 3: product j of

@@ -155,6 +155,77 @@ __device__ void nid_plan_mixed(double eps, double tr, int kcap, double cost_fp64
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Residual-certified plan.  The mixed plan's fp64 residual r = b - M x0 is a
+// certificate in itself: |M^-1| <= 1 gives |w - x0| = |M^-1 r| <= |r| whatever produced x0, so
+// the first solve needs no a-priori bound and may run on a guessed interval [1, 1 + eps1],
+//   eps1 = min(e2, phi tr(E) Lambda / sum_j |x_j|^2)
+// (the value lambda_max(E) takes when the D_j are equal, times phi = 8; the thresholded bound
+// eps is 15-23 times lambda_max(E) on the C3 chain).  Only the correction solve stays on the
+// certified interval [1, 1 + e2]; its K2 is chosen after the residual pass (k_nid_k2).  Here K1
+// is a prediction: rho^(K1) = eta + t_K1(eps1)(1 + eta) stands for |r| / |w|, K2^ is the least
+// K2 with err2(K2) rho^ <= tol, err2(K2) = eta + t_K2(e2)(1 + eta), and (K1, K2^) is priced as
+// nid_plan_mixed prices its plans, with the beta pass's credit when rho^ is within kBeta32Tol.
+// The plan is taken when it is within the cap and its cost is at most `limit` (the caller: no
+// dearer than the sweep's a-priori mixed plan -- eps1 <= e2, so there always is one -- or
+// cheaper than its fp64 plan; any_cost: whenever a K1 qualifies).  The residual usually
+// certifies fewer iterates than predicted, never more than the a-priori plan's where the
+// guess holds.  Same one-wave search as nid_plan_mixed.
+// ---------------------------------------------------------------------------------------
+__device__ void nid_plan_resid(double eta, double e2, double eps1, int kcap, double limit,
+                               const NidState *nid, bool any_cost, double bsave, int &K1,
+                               int &K2) {
+    const int lane = threadIdx.x & 63;
+    K1 = K2 = 0;
+    if (!(e2 < 1e300) || !(eps1 > 0.0) || kcap < 1) return;
+    const ChebConst c1 = cheb_const(eps1), c2 = cheb_const(e2);
+    const int kmax = kcap < 64 ? kcap : 64;
+    const double a1 = acosh(c1.sigma1), a2 = acosh(c2.sigma1);
+    const bool in = lane + 1 <= kmax;
+    const double t1 = in ? sqrt(1.0 + eps1) / cosh((lane + 1) * a1) * (1.0 + 1e-12) : HUGE_VAL;
+    const double t2 = in ? sqrt(1.0 + e2) / cosh((lane + 1) * a2) * (1.0 + 1e-12) : HUGE_VAL;
+    const double step32 = nid->c32 + nid->cstep, step64 = nid->c64 + nid->cstep;
+    const double cap = (kcap - 1) * step64;
+    const int k1 = lane + 1;
+    const double rho = eta + t1 * (1.0 + eta);
+    const double need = kNidTol / rho;
+    int lo = 1, hi = kmax + 1;
+#pragma unroll
+    for (int it = 0; it < 7; ++it) {
+        const int mid = (lo + hi) >> 1;
+        const double tm = __shfl(t2, (mid < kmax ? mid : kmax) - 1, 64);
+        if (lo < hi) {
+            if (eta + tm * (1.0 + eta) <= need)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+    }
+    const int k2 = lo <= kmax ? lo : 0;
+    double cost = (k1 <= kmax && rho < 1.0 && k2)
+                      ? (k1 - 1) * step32 + step64 + (k2 - 1) * step32
+                      : HUGE_VAL;
+    if (!(cost < cap * (1.0 - 1e-9))) cost = HUGE_VAL;
+    if (rho * (1.0 + 1e-6) <= kBeta32Tol) cost -= bsave;
+    if (!any_cost && !(cost <= limit)) cost = HUGE_VAL;
+    double bc = cost;
+    int bk1 = k1, bk2 = k2;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oc = __shfl_xor(bc, o, 64);
+        const int ok1 = __shfl_xor(bk1, o, 64), ok2 = __shfl_xor(bk2, o, 64);
+        if (oc < bc || (oc == bc && ok1 < bk1)) {
+            bc = oc;
+            bk1 = ok1;
+            bk2 = ok2;
+        }
+    }
+    if (bc < HUGE_VAL) {
+        K1 = bk1;
+        K2 = bk2;
+    }
+}
+
 // bb_set_tuning key 16 (benchmarking only): a forced iteration count K > 0 replaces the
 // certified one on the near-identity path (the solve is then no longer certified), so that the
 // per-rank proxy of an N-GPU C3 job runs a C3 rank's product count
@@ -223,7 +294,6 @@ __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launch
             eta = 0.0;
         }
     }
-    if ((threadIdx.x & 63) != 0) return;
     int b32 = 0;
     if (b32_pays && mode > 0) {
         double bound = HUGE_VAL;
@@ -233,17 +303,65 @@ __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launch
             bound = cheb_bound_at(eps, mode) + cheb_bound_at(eps, mode - 1);
         b32 = bound * (1.0 + 1e-6) <= kBeta32Tol;
     }
+    // the residual-certified plan against the a-priori plan just chosen, which
+    // stays behind as the sweep's redo (so only where that plan is a Chebyshev one)
+    int resid = 0;
+    const int fb_mode = mode, fb_k2 = k2, fb_b32 = b32;
+    const double fb_eta = eta;
+    double ecb2 = ecb;
+    if (allow && (allow_mixed & kAllowMixed) && (allow_mixed & kAllowResid) &&
+        g_dev_nid_force_k == 0 && mode > 0 && (K == 0 || K > 2)) {
+        const double tr = round_up_12(red[kNidTS] / sc->sig2 * (1.0 + 1e-6));
+        const double etam = (2.0 * kU32 * sqrt(tr * eps) + kU32 * kU32 * tr) * (1.0 + 1e-6);
+        const double e2 = eps + etam;
+        const double phi = ldexp(8.0, -4 * (allow_mixed >> kResidPhiShift));
+        double eps1 = e2;
+        if (lam > 0.0 && lam < HUGE_VAL && nid->sum_cn > 0.0)
+            eps1 = fmin(e2, phi * tr * lam / nid->sum_cn);
+        const double step32 = nid->c32 + nid->cstep, step64 = nid->c64 + nid->cstep;
+        const double today = (k2 ? (mode - 1) * step32 + step64 + (k2 - 1) * step32
+                                 : (mode - 1) * step64) -
+                             (b32 ? bsave : 0.0);
+        int k1r, k2r;
+        nid_plan_resid(etam, e2, eps1, k_launched, today * (k2 ? 1.0 + 1e-9 : 1.0 - 1e-9), nid,
+                       (allow_mixed & kResidAnyCost) != 0, bsave, k1r, k2r);
+        if (k2r > 0) {
+            resid = 1;
+            mode = k1r;
+            k2 = k2r;           // the prediction: k_nid_k2 sets the certified one
+            b32 = b32_pays;     // the residual pass banks its dots; k_nid_k2 decides
+            eta = etam;
+            ecb = eps1;
+            ecb2 = e2;
+        }
+    }
+    if ((threadIdx.x & 63) != 0) return;
     nid->eps = eps;
     nid->mode = mode;
     nid->k2 = k2;
     nid->b32 = b32;
-    nid->n_beta32 += (unsigned long long)b32;
+    if (!resid) nid->n_beta32 += (unsigned long long)b32;
     nid->eta = eta;
-    const ChebConst c = cheb_const(ecb);
+    const ChebConst c = cheb_const(ecb), cc = cheb_const(ecb2);
     nid->theta = c.theta;
     nid->delta = c.delta;
     nid->sigma1 = c.sigma1;
-    if (mode && k2) {
+    nid->theta2 = cc.theta;
+    nid->delta2 = cc.delta;
+    nid->sigma12 = cc.sigma1;
+    nid->e2 = ecb2;
+    nid->resid = resid;
+    nid->fb_mode = fb_mode;
+    nid->fb_k2 = fb_k2;
+    nid->fb_b32 = fb_b32;
+    nid->fb_eta = fb_eta;
+    if (resid) {
+        // k_nid_k2 counts the correction's products (or k_nid_adopt the redo's)
+        nid->n_cheb += 1;
+        nid->n_mixed += 1;
+        nid->n_products += 1ull;
+        nid->n_products32 += (unsigned long long)(mode - 1);
+    } else if (mode && k2) {
         nid->n_cheb += 1;
         nid->n_mixed += 1;
         nid->n_products += 1ull;  // the fp64 residual pass
@@ -262,8 +380,8 @@ __device__ void nid_finish(const double *red, const DevScalars *sc, int k_launch
     // (an event marker in the stream cost ~6 us of idle device per sweep)
     if (tag_seq && mode_host)
         __hip_atomic_store((unsigned long long *)(mode_host + 2),
-                           (tag_seq << 16) | ((unsigned long long)mode << 8) |
-                               (unsigned)(k2 | (b32 << 7)),
+                           (tag_seq << 16) | ((unsigned long long)(mode | (resid << 7)) << 8) |
+                               (unsigned)(k2 | (b32 << 7)),  // mode <= 64: resid in its bit 7
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -454,6 +572,17 @@ __device__ __forceinline__ int rs_block(int xcd) {
 int g_rs_xcd = 1;
 static int rowsum_rw(int nparts) { return nparts >= 128 ? 8 : 64; }
 
+// out[workgroup] = the sum of v^2 over the workgroup's RW rows (threads [0, RW), all of them
+// active: lanes of wave 0), by a fixed xor tree: the partials of |b|^2 and |r|^2 that k_nid_k2
+// adds in workgroup order
+template <int RW>
+__device__ __forceinline__ void rows_sq_part(double v, double *__restrict__ out) {
+    double s = v * v;
+#pragma unroll
+    for (int o = RW / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, RW);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
 // r_0 = y / sig - (X u / sig + delta), x_1 = d_0 = r_0 / theta (x_0 = 0).  X u arrives as
 // nparts partial n-vectors (the fused lambda launch, k_eapply<XU>, or the sparse row pass
 // with nparts = 1).
@@ -461,17 +590,19 @@ template <int RW>
 __global__ __launch_bounds__(kRsThreads) void k_cheb_init(
     const double *__restrict__ xu_part, int nparts, int n, int n_pad,
     const double *__restrict__ y, const DevScalars *sc, Key key, uint64_t t, const NidState *nid,
-    double *x, double *r, double *d, double *b, double *xu_out, int xcd) {
+    double *x, double *r, double *d, double *b, double *xu_out, int xcd, double *sqb) {
     if (nid->mode == 0) return;
     const int i = rs_block(xcd) * RW + (int)threadIdx.x;
     const double xu = part_rowsum_rw<RW>(xu_part, nparts, n_pad, rs_block(xcd) * RW);
-    if ((int)threadIdx.x >= RW || i >= n_pad) return;
+    if ((int)threadIdx.x >= RW) return;
     double rhs = 0.0;
     if (i < n) {
         const double sig = sqrt(sc->sig2);
         const double delta = normal_at(key, t, KIND_DELTA, (uint64_t)i);
         rhs = y[i] / sig - (xu / sig + delta);  // k_form_m's right-hand side
     }
+    if (sqb) rows_sq_part<RW>(rhs, sqb);
+    if (i >= n_pad) return;
     const double d0 = rhs / nid->theta;
     r[i] = rhs;
     d[i] = d0;
@@ -502,9 +633,12 @@ __global__ __launch_bounds__(kRsThreads) void k_cheb_step(
     const double dv = d[i];
     const double qv = dv + e / sc->sig2;
     const double rv = r[i] - qv;
-    const double s1 = nid->sigma1;
+    // the correction solve's interval is the certified one (the same scalars unless the first
+    // solve ran on a guessed interval)
+    const double s1 = phase == 2 ? nid->sigma12 : nid->sigma1;
+    const double dl = phase == 2 ? nid->delta2 : nid->delta;
     const double rho0 = cheb_rho(s1, j - 1), rho1 = 1.0 / (2.0 * s1 - rho0);
-    const double dn = rho1 * rho0 * dv + (2.0 * rho1 / nid->delta) * rv;
+    const double dn = rho1 * rho0 * dv + (2.0 * rho1 / dl) * rv;
     r[i] = rv;
     d[i] = dn;
     const double xn = x[i] + dn;
@@ -522,21 +656,137 @@ template <int RW>
 __global__ __launch_bounds__(kRsThreads) void k_cheb_restart(
     const double *__restrict__ part, int nparts, int n_pad, const DevScalars *sc,
     const NidState *nid, const double *__restrict__ b, double *x, double *r, double *d, int xcd,
-    Beta32Vecs bv) {
+    Beta32Vecs bv, double *sqr) {
     if (nid->k2 == 0 || nid->mode == 0) return;
     const int i = rs_block(xcd) * RW + (int)threadIdx.x;
     const double e = part_rowsum_rw<RW>(part, nparts, n_pad, rs_block(xcd) * RW);
-    if ((int)threadIdx.x >= RW || i >= n_pad) return;
-    const double xv = x[i];
-    const double rv = b[i] - (xv + e / sc->sig2);
-    const double dv = rv / nid->theta;
+    if ((int)threadIdx.x >= RW) return;
+    const bool in = i < n_pad;
+    const double xv = in ? x[i] : 0.0;
+    const double rv = in ? b[i] - (xv + e / sc->sig2) : 0.0;
+    if (sqr) rows_sq_part<RW>(rv, sqr);
+    if (!in) return;
+    const double dv = rv / nid->theta2;
     r[i] = rv;
     d[i] = dv;
     x[i] = xv + dv;
     if (bv.c) {
         bv.c[i] = dv;
-        if (nid->k2 == 1 && nid->b32) beta32_xb(bv, sc, i, xv + dv);
+        // (a residual-certified sweep learns K2 and b32 after this launch: k_nid_k2 writes it)
+        if (nid->k2 == 1 && nid->b32 && !nid->resid) beta32_xb(bv, sc, i, xv + dv);
     }
+}
+
+// The residual-certified plan's second decision, one workgroup after the
+// restart.  With |M^-1| <= 1 the exact correction c* = M^-1 r has |c*| <= |r|; K2 iterates on M~
+// from r give |c - c*| <= err2(K2) |c*|, err2 = eta + t_K2(e2)(1 + eta) (s6.6's bound for a solve
+// on M~ from any right-hand side); and |w| >= |b| / (1 + eps).  So
+//   |x0 + c - w| / |w| <= err2(K2) ratio,   ratio = |r| (1 + eps)(1 + 1e-6) / |b|,
+// and the least K2 <= kcap with err2(K2) ratio <= 2^-56 certifies the sweep, whatever interval
+// the first solve guessed.  b32 (s6.7) follows from |c| <= (1 + err2) |r|.  No such K2, or a
+// ratio that is not below 1 (the guess was wrong): mode = k2 = 0 switches the launches already
+// queued off and the tag tells the host to redo the sweep on its a-priori plan.
+// sqb / sqr: Gb / Gr workgroup partials, added in a fixed order (lane l takes l, l + 64, ...,
+// then the wave's xor tree): every choice here is a function of the chain's state.
+constexpr int kK2Threads = 1024;
+__global__ __launch_bounds__(kK2Threads) void k_nid_k2(
+    const double *__restrict__ sqb, int Gb, const double *__restrict__ sqr, int Gr, int kcap,
+    const DevScalars *sc, NidState *nid, Beta32Vecs bv, const double *__restrict__ w, int n_pad,
+    unsigned long long *tag, unsigned long long seq) {
+    __shared__ int sh[3];
+    __shared__ double shr;
+    if (!nid->resid || nid->mode == 0 || nid->k2 == 0) return;
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < 64) {
+        const double eps = nid->eps, eta = nid->eta, e2 = nid->e2;
+        const int wanted = nid->b32;
+        double bb = 0.0, rr = 0.0;
+        for (int g = lane; g < Gb; g += 64) bb += sqb[g];
+        for (int g = lane; g < Gr; g += 64) rr += sqr[g];
+        bb = wave_sum_all(bb);
+        rr = wave_sum_all(rr);
+        // b = 0: w = 0 and r = 0, certified by any K2
+        double ratio = rr == 0.0 ? 0.0 : sqrt(rr) * (1.0 + eps) * (1.0 + 1e-6) / sqrt(bb);
+        const int kmax = kcap < 64 ? kcap : 64;
+        const ChebConst c = cheb_const(e2);
+        const double tk = lane + 1 <= kmax ? sqrt(1.0 + e2) / cosh((lane + 1) * acosh(c.sigma1)) *
+                                                 (1.0 + 1e-12)
+                                           : HUGE_VAL;
+        const double err2 = eta + tk * (1.0 + eta);
+        const bool ok = ratio < 1.0 && lane + 1 <= kmax && err2 * ratio <= kNidTol;
+        const unsigned long long m = __ballot(ok);
+        const int K2 = m ? __ffsll((long long)m) : 0;
+        const double e2k = __shfl(err2, K2 ? K2 - 1 : 0, 64);
+        const int b32 = K2 && wanted && (1.0 + e2k) * ratio * (1.0 + 1e-6) <= kBeta32Tol;
+        if (lane == 0) {
+            sh[0] = K2;
+            sh[1] = b32;
+            shr = ratio;
+        }
+    }
+    __syncthreads();
+    const int K2 = sh[0], b32 = sh[1];
+    if (K2 == 1 && b32 && bv.c)  // the restart was the last step: X beta from the n-vectors
+        for (int i = threadIdx.x; i < n_pad; i += kK2Threads) beta32_xb(bv, sc, i, w[i]);
+    if (threadIdx.x != 0) return;
+    const int mode = nid->mode;
+    nid->ratio = shr;
+    unsigned long long word;
+    if (K2) {
+        nid->k2 = K2;
+        nid->b32 = b32;
+        nid->n_beta32 += (unsigned long long)b32;
+        nid->n_products32 += (unsigned long long)(K2 - 1);
+        nid->n_resid += 1;
+        word = ((unsigned long long)mode << 8) | (unsigned)(K2 | (b32 << 7));
+    } else {
+        nid->mode = 0;
+        nid->k2 = 0;
+        nid->b32 = 0;
+        nid->n_redo += 1;
+        word = (1ull << 16) | ((unsigned long long)nid->fb_mode << 8) |
+               (unsigned)(nid->fb_k2 | (nid->fb_b32 << 7));
+    }
+    __hip_atomic_store(tag, (seq << 24) | word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// A redo: the sweep's a-priori plan into the live decision words -- exactly
+// what nid_finish would have written without the residual-certified plan -- and its counters
+__global__ __launch_bounds__(64) void k_nid_adopt(NidState *nid) {
+    if (threadIdx.x != 0 || nid->resid == 0) return;
+    const int mode = nid->fb_mode, k2 = nid->fb_k2;
+    nid->mode = mode;
+    nid->k2 = k2;
+    nid->b32 = nid->fb_b32;
+    nid->n_beta32 += (unsigned long long)nid->fb_b32;
+    nid->eta = nid->fb_eta;
+    const ChebConst c = cheb_const(k2 ? nid->e2 : nid->eps);
+    nid->theta = nid->theta2 = c.theta;
+    nid->delta = nid->delta2 = c.delta;
+    nid->sigma1 = nid->sigma12 = c.sigma1;
+    nid->resid = 0;
+    // nid_finish counted a mixed sweep, its residual pass and the guessed solve's fp32 products
+    // (which ran); the redo's own passes on top
+    if (k2) {
+        nid->n_products += 1ull;
+        nid->n_products32 += (unsigned long long)(mode - 1 + k2 - 1);
+    } else {
+        nid->n_mixed -= 1;
+        nid->n_products += (unsigned long long)(mode - 1);
+    }
+}
+
+// the initial iterate again from the stored right-hand side: x = d = b / theta, r = b
+__global__ __launch_bounds__(256) void k_cheb_reinit(const NidState *nid,
+                                                     const double *__restrict__ b, int n_pad,
+                                                     double *x, double *r, double *d) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (nid->mode == 0 || i >= n_pad) return;
+    const double rhs = b[i];
+    const double d0 = rhs / nid->theta;
+    r[i] = rhs;
+    d[i] = d0;
+    x[i] = d0;
 }
 
 // out[i] = sum of the nparts partials of row i (setup: power iteration on X X')
@@ -846,15 +1096,15 @@ void launch_nid_xu(hipStream_t s, const double *X, int ldx, const double *u, int
 void launch_cheb_init(hipStream_t s, const double *xu_part, int nparts, int n, int n_pad,
                       const double *y, const DevScalars *sc, uint64_t k0, uint64_t k1,
                       uint64_t t, const NidState *nid, double *x, double *r, double *d,
-                      double *b, double *xu) {
+                      double *b, double *xu, double *sqb) {
     if (rowsum_rw(nparts) == 8)
         k_cheb_init<8><<<(n_pad + 7) / 8, kRsThreads, 0, s>>>(xu_part, nparts, n, n_pad, y, sc,
                                                               Key{k0, k1}, t, nid, x, r, d, b,
-                                                              xu, g_rs_xcd);
+                                                              xu, g_rs_xcd, sqb);
     else
         k_cheb_init<64><<<(n_pad + 63) / 64, kRsThreads, 0, s>>>(xu_part, nparts, n, n_pad, y,
                                                                  sc, Key{k0, k1}, t, nid, x, r, d,
-                                                                 b, xu, g_rs_xcd);
+                                                                 b, xu, g_rs_xcd, sqb);
 }
 
 void launch_cheb_step(hipStream_t s, const double *part, int nparts, int n_pad,
@@ -871,14 +1121,34 @@ void launch_cheb_step(hipStream_t s, const double *part, int nparts, int n_pad,
 
 void launch_cheb_restart(hipStream_t s, const double *part, int nparts, int n_pad,
                          const DevScalars *sc, const NidState *nid, const double *b, double *x,
-                         double *r, double *d, const Beta32Vecs *bv) {
+                         double *r, double *d, const Beta32Vecs *bv, double *sqr) {
     const Beta32Vecs v = bv ? *bv : Beta32Vecs{};
     if (rowsum_rw(nparts) == 8)
         k_cheb_restart<8><<<(n_pad + 7) / 8, kRsThreads, 0, s>>>(part, nparts, n_pad, sc, nid, b,
-                                                                 x, r, d, g_rs_xcd, v);
+                                                                 x, r, d, g_rs_xcd, v, sqr);
     else
         k_cheb_restart<64><<<(n_pad + 63) / 64, kRsThreads, 0, s>>>(part, nparts, n_pad, sc, nid,
-                                                                    b, x, r, d, g_rs_xcd, v);
+                                                                    b, x, r, d, g_rs_xcd, v, sqr);
+}
+
+// the workgroups of launch_cheb_init / launch_cheb_restart over nparts partials: one partial of
+// |b|^2 / |r|^2 each
+int cheb_sq_parts(int n_pad, int nparts) {
+    const int rw = rowsum_rw(nparts);
+    return (n_pad + rw - 1) / rw;
+}
+
+void launch_nid_k2(hipStream_t s, const double *sqb, int Gb, const double *sqr, int Gr, int kcap,
+                   const DevScalars *sc, NidState *nid, const Beta32Vecs *bv, const double *w,
+                   int n_pad, unsigned long long *tag, unsigned long long seq) {
+    k_nid_k2<<<1, kK2Threads, 0, s>>>(sqb, Gb, sqr, Gr, kcap, sc, nid, bv ? *bv : Beta32Vecs{}, w,
+                                      n_pad, tag, seq);
+}
+
+void launch_nid_redo(hipStream_t s, NidState *nid, const double *b, int n_pad, double *x,
+                     double *r, double *d) {
+    k_nid_adopt<<<1, 64, 0, s>>>(nid);
+    k_cheb_reinit<<<(n_pad + 255) / 256, 256, 0, s>>>(nid, b, n_pad, x, r, d);
 }
 
 void launch_eapply(hipStream_t s, const double *X, int ldx, int n_pad, int p_loc,

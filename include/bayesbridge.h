@@ -654,6 +654,18 @@ void bb_set_trace_budget(long long bytes);
  * and 26).  Under one setting, chain c of a batch is bit for bit the c-th of sequential
  * single-chain calls, with every instance.  p > 32, p > n and sharded triangle engines are as
  * they are without the key.
+ * key 29 (the residual-certified mixed plan): an unsharded dense engine that holds
+ * the fp32 copy of X and decides under the synchronous protocol with the polled tag (keys 8, 10,
+ * 11) may run the mixed plan's first solve on a guessed, tighter spectrum interval and choose the
+ * correction's iterates from the norm of the fp64 residual, which certifies the same 2^-56 whatever
+ * the first solve reached; a sweep whose residual certifies nothing is redone on the a-priori plan
+ * (the same result as with the key off).  Never (0: the plan search of keys 10 and 24 bit for
+ * bit), where the cost model says it is cheaper and an fp32 pass over X costs more than four
+ * launches (1, the default: C3's shape, not designs an eighth its size), wherever a first solve
+ * qualifies (2, for tests at small shapes), or that with the guess factor 8 divided by 16^(v - 2)
+ * (v = 3 .. 8, tests of the redo).  lambda / tau / sig2 of a sweep are the same bits, beta agrees
+ * to the solves' common tolerance; shards, group members and sparse engines are unaffected.
+ * (The key is 29, not 28: a test pins 28 as an unknown key.)
  * A negative value changes nothing.  Returns the previous value, or -1 for an unknown key. */
 int bb_set_tuning(int key, int value);
 /* Test hook: the k-th interrupt poll from now reports an interrupt (k >= 0; -1 clears). */
@@ -752,6 +764,12 @@ int bb_engine_nid_mixed(bb_engine *e, unsigned long long *mixed_sweeps,
 /* The fp32 beta pass (bb_set_tuning key 24): sweeps that took it since the
  * engine was created, and whether the latest sweep did. */
 int bb_engine_nid_beta32(bb_engine *e, unsigned long long *beta32_sweeps, int *b32);
+
+/* The residual-certified plan (bb_set_tuning key 29): sweeps whose correction was
+ * chosen from the fp64 residual, sweeps redone on the a-priori plan because the residual certified
+ * nothing (counts since creation), and the latest certificate's |r| (1 + eps)(1 + 1e-6) / |b|. */
+int bb_engine_nid_resid(bb_engine *e, unsigned long long *resid_sweeps,
+                        unsigned long long *redo_sweeps, double *ratio);
 
 /* Error flags raised on device (rejection-loop caps, non-SPD factorisations). */
 int bb_engine_error_flags(bb_engine *e, uint32_t *flags);

@@ -27,7 +27,7 @@ __all__ = ["bridge_reg_stb", "bridge_reg", "retstable_ld", "set_seed", "get_rng_
            "sample_lambda", "retstable_batch", "gram", "chol_solve", "bridge_reg_stb_chains",
            "bridge_reg_tri_chains", "ChainBatch", "compute_units",
            "bridge_reg_stb_chains_summary", "bridge_reg_tri_chains_summary", "trace_summary",
-           "bridge_reg_logit_chains", "bridge_reg_logit_chains_summary"]
+           "bridge_reg_logit_chains", "bridge_reg_logit_chains_summary", "trace_quantiles"]
 
 _lib: Optional[ctypes.CDLL] = None
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -79,6 +79,9 @@ EXPORTED_SYMBOLS = [
     "bridge_regression_chains_summary", "bb_chains_summary_reset", "bb_chains_summary_add",
     "bb_chains_summary_get", "bb_trace_summary", "bridge_reg_logit_chains",
     "bridge_reg_logit_chains_summary", "bb_chains_get_omega", "bb_set_em_scratch_budget",
+    "bridge_reg_stable_chains_summary_q", "bridge_regression_chains_summary_q",
+    "bridge_reg_logit_chains_summary_q", "bb_chains_quantiles_reset", "bb_chains_quantiles_get",
+    "bb_trace_quantiles", "bb_quantile_bin",
 ]
 
 
@@ -222,6 +225,17 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bb_chains_summary_get.argtypes = [c.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip]
     L.bb_trace_summary.argtypes = [_dp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, _dp, _dp,
                                    _dp, _dp, _dp]
+    quant = [_dp, _ip] + [_dp] * 6  # probs, nprobs, centre, zlo, zhi, below, inbin, counts
+    L.bridge_reg_stable_chains_summary_q.argtypes = (
+        L.bridge_reg_stable_chains_summary.argtypes + quant)
+    L.bridge_regression_chains_summary_q.argtypes = (
+        L.bridge_regression_chains_summary.argtypes + quant)
+    L.bridge_reg_logit_chains_summary_q.argtypes = (
+        L.bridge_reg_logit_chains_summary.argtypes + quant)
+    L.bb_chains_quantiles_reset.argtypes = [c.c_void_p]
+    L.bb_chains_quantiles_get.argtypes = [c.c_void_p, _dp, c.c_int] + [_dp] * 6
+    L.bb_trace_quantiles.argtypes = [_dp, c.c_int, c.c_int, c.c_int, c.c_int, _dp, c.c_int] + [_dp] * 6
+    L.bb_quantile_bin.argtypes = [c.c_double, _ip, _dp, _dp]
     L.bb_chains_set_tri_state.argtypes = [c.c_void_p, c.c_int, _dp]
     L.bb_chains_get_tri_basis.argtypes = [c.c_void_p, _dp, _dp, _dp]
     L.bb_chains_threads.argtypes = [c.c_void_p]
@@ -667,9 +681,55 @@ def _summary_result(raw, P: int, nsamp: int, maxlag: int, runtime: float):
     return out
 
 
+QUANTILE_MAX_PROBS = 64
+
+
+def _check_probs(probs, what: str) -> np.ndarray:
+    """The probabilities of a quantile request as a float64 vector: 1 to 64 values in [0, 1]."""
+    pr = np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel().copy()
+    if pr.size < 1:
+        raise ValueError(f"{what}: probs is empty")
+    if pr.size > QUANTILE_MAX_PROBS:
+        raise ValueError(f"{what}: at most {QUANTILE_MAX_PROBS} probabilities per call "
+                         f"(got {pr.size})")
+    if not np.all((pr >= 0.0) & (pr <= 1.0)):  # NaN fails both comparisons
+        raise ValueError(f"{what}: every probability must be in [0, 1] (got {pr.tolist()})")
+    return pr
+
+
+def _quantile_buffers(Q: int, probs: np.ndarray):
+    """The caller-allocated outputs of a quantile selection ([Q][nprobs] in C order).  NaN
+    until written."""
+    n = probs.size
+    raw = {k: np.full((Q, n), np.nan) for k in ("zlo", "zhi", "below", "inbin")}
+    raw.update(probs=probs, centre=np.full(Q, np.nan), counts=np.full((Q, 6), np.nan))
+    return raw
+
+
+def _quantile_args(raw, dot_c: bool = False):
+    """The trailing arguments of a quantile call: probs, nprobs (a pointer for the .C entries)
+    and the six outputs."""
+    n = raw["probs"].size
+    return [_p(raw["probs"]), ctypes.byref(ctypes.c_int(n)) if dot_c else n, _p(raw["centre"]),
+            _p(raw["zlo"]), _p(raw["zhi"]), _p(raw["below"]), _p(raw["inbin"]), _p(raw["counts"])]
+
+
+def _quantile_result(raw):
+    """The quantile keys of a result: the raw selection, the sign probabilities and the
+    point estimates with their brackets (diagnostics.quantiles_from_bins)."""
+    from .diagnostics import quantiles_from_bins
+
+    out = dict(raw)
+    out.update(quantiles_from_bins(raw["probs"], raw["centre"], raw["zlo"], raw["zhi"],
+                                   raw["below"], raw["inbin"], raw["counts"]))
+    return out
+
+
 def _chains_summary(entry: str, tri: bool, y, X, nsamp, nchains, alpha, sig2_shape, sig2_scale,
                     nu_shape, nu_rate, alpha_a, alpha_b, sig2_true, tau_true, burn, ortho,
-                    betaburn, maxlag):
+                    betaburn, maxlag, probs=None):
+    if probs is not None:
+        probs = _check_probs(probs, entry)
     L = library()
     _require_gpu()
     y = np.asarray(y, dtype=np.float64).ravel()
@@ -695,19 +755,25 @@ def _chains_summary(entry: str, tri: bool, y, X, nsamp, nchains, alpha, sig2_sha
             d(sig2_scale), d(nu_shape), d(nu_rate), d(alpha_a), d(alpha_b), d(sig2_true),
             d(tau_true), d(alpha), i(P), i(N), i(M), i(burn), ctypes.byref(rt),
             i(1 if ortho else 0)]
-    if tri:
-        L.bridge_regression_chains_summary(*args, i(betaburn), i(0), i(K))
-    else:
-        L.bridge_reg_stable_chains_summary(*args, i(K))
+    args += [i(betaburn), i(0), i(K)] if tri else [i(K)]
+    qraw = None
+    if probs is not None:
+        qraw = _quantile_buffers(P + 3, probs)
+        args += _quantile_args(qraw, dot_c=True)
+    name = "bridge_regression_chains_summary" if tri else "bridge_reg_stable_chains_summary"
+    getattr(L, name if probs is None else name + "_q")(*args)
     if np.isnan(raw["mean"]).all() and rt.value == 0.0:
         raise RuntimeError(f"{entry}: the call returned no summaries: {_err()}")
-    return _summary_result(raw, P, M, lag, rt.value)
+    out = _summary_result(raw, P, M, lag, rt.value)
+    if qraw is not None:
+        out.update(_quantile_result(qraw))
+    return out
 
 
 def bridge_reg_stb_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0,
                                   sig2_scale=0.0, nu_shape=2.0, nu_rate=2.0, alpha_a=1.0,
                                   alpha_b=1.0, sig2_true=0.0, tau_true=0.0, burn=500,
-                                  ortho=False, maxlag=None):
+                                  ortho=False, maxlag=None, probs=None):
     """``bridge_reg_stb_chains`` returning posterior summaries instead of traces, through
     ``.C("bridge_reg_stable_chains_summary", ...)``: the chains are bit for bit those of the
     trace call under the same key, each ring fill is reduced on the device and nothing but the
@@ -721,23 +787,32 @@ def bridge_reg_stb_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.
     hvar (K x Q x 2, the halves of split R-hat), flags (K), names, nsamp, maxlag, p, and the keys
     of ``diagnostics.sum_stat_chains`` for the coefficients (mean, sd, ess, esr, rhat,
     ess_summary, esr_summary, runtime, chains), so a script can switch between the two calls.
-    ``maxlag=None`` is min(63, coda's default order)."""
+    ``maxlag=None`` is min(63, coda's default order).
+
+    ``probs`` (1 to 64 probabilities in [0, 1]) takes ``.C("bridge_reg_stable_chains_summary_q",
+    ...)`` instead: the same chains and summaries, and pooled over all chains, from a histogram
+    of every draw built on the device (include/bayesbridge.h), the keys probs, centre (Q), zlo,
+    zhi, below, inbin (Q x nprobs: the bin of x - centre that holds R's type-1 quantile, a
+    guaranteed bracket, with the counts below it and in it), counts (Q x 6: N, NaN, negative,
+    positive, zero-bin, overflow), prob_pos, prob_neg (Q) and quantile, quantile_lo,
+    quantile_hi (Q x nprobs: ``diagnostics.quantiles_from_bins``)."""
     return _chains_summary("bridge_reg_stb_chains_summary", False, y, X, nsamp, nchains, alpha,
                            sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
-                           sig2_true, tau_true, burn, ortho, 0, maxlag)
+                           sig2_true, tau_true, burn, ortho, 0, maxlag, probs)
 
 
 def bridge_reg_tri_chains_summary(y, X, nsamp, nchains, alpha=0.5, sig2_shape=0.0,
                                   sig2_scale=0.0, nu_shape=2.0, nu_rate=2.0, alpha_a=1.0,
                                   alpha_b=1.0, sig2_true=0.0, tau_true=0.0, burn=500,
-                                  ortho=False, betaburn=0, maxlag=None):
+                                  ortho=False, betaburn=0, maxlag=None, probs=None):
     """``bridge_reg_tri_chains`` returning posterior summaries instead of traces, through
     ``.C("bridge_regression_chains_summary", ...)``; see ``bridge_reg_stb_chains_summary``.
     With alpha unknown (``alpha <= 0``) the chains run as one batch after
-    ``set_fused_tri_alpha(True)`` (P <= 32, P <= N), else one after another."""
+    ``set_fused_tri_alpha(True)`` (P <= 32, P <= N), else one after another.  ``probs`` adds
+    the pooled quantiles (``.C("bridge_regression_chains_summary_q", ...)``)."""
     return _chains_summary("bridge_reg_tri_chains_summary", True, y, X, nsamp, nchains, alpha,
                            sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a, alpha_b,
-                           sig2_true, tau_true, burn, ortho, betaburn, maxlag)
+                           sig2_true, tau_true, burn, ortho, betaburn, maxlag, probs)
 
 
 def trace_summary(x, maxlag, chunk=None):
@@ -757,6 +832,23 @@ def trace_summary(x, maxlag, chunk=None):
                               _p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]),
                               _p(raw["hmean"]), _p(raw["hvar"])), "bb_trace_summary")
     return raw
+
+
+def trace_quantiles(x, probs, chunk=None):
+    """The quantile-sketch kernels on host data (bb_trace_quantiles): x is (K, M, Q) (a (M, Q)
+    array is one chain), pooled over the chains and accumulated ``chunk`` samples at a time
+    (None: all at once).  Returns the quantile keys of ``bridge_reg_stb_chains_summary``."""
+    probs = _check_probs(probs, "trace_quantiles")
+    L = library()
+    _require_gpu()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    K, M, Q = x.shape
+    raw = _quantile_buffers(Q, probs)
+    _check(L.bb_trace_quantiles(_p(x), K, M, Q, int(M if chunk is None else chunk),
+                                *_quantile_args(raw)), "bb_trace_quantiles")
+    return _quantile_result(raw)
 
 
 def bridge_reg_logit(y, X, nsamp, alpha=0.5, nu_shape=2.0, nu_rate=2.0, alpha_a=1.0,
@@ -843,11 +935,14 @@ def bridge_reg_logit_chains(y, X, nsamp, nchains, alpha=0.5, nu_shape=2.0, nu_ra
 
 def bridge_reg_logit_chains_summary(y, X, nsamp, nchains, alpha=0.5, nu_shape=2.0, nu_rate=2.0,
                                     alpha_a=1.0, alpha_b=1.0, tau_true=0.0, burn=500,
-                                    maxlag=None):
+                                    maxlag=None, probs=None):
     """``bridge_reg_logit_chains`` returning posterior summaries instead of traces, through
     ``.C("bridge_reg_logit_chains_summary", ...)``; the sig2 column is the constant 1.  See
-    ``bridge_reg_stb_chains_summary`` for what is returned."""
+    ``bridge_reg_stb_chains_summary`` for what is returned and for ``probs``
+    (``.C("bridge_reg_logit_chains_summary_q", ...)``)."""
     entry = "bridge_reg_logit_chains_summary"
+    if probs is not None:
+        probs = _check_probs(probs, entry)
     L = library()
     _require_gpu()
     y, Xf, P, N, M, K = _logit_chains_args(entry, y, X, nsamp, nchains, nu_shape, nu_rate,
@@ -859,14 +954,22 @@ def bridge_reg_logit_chains_summary(y, X, nsamp, nchains, alpha=0.5, nu_shape=2.
     d = lambda v: ctypes.byref(ctypes.c_double(float(v)))  # noqa: E731
     i = lambda v: ctypes.byref(ctypes.c_int(int(v)))  # noqa: E731
     rt = ctypes.c_double(0.0)
-    L.bridge_reg_logit_chains_summary(
-        _p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]), _p(raw["hmean"]), _p(raw["hvar"]),
-        raw["flags"].ctypes.data_as(_ip), i(lag), _p(y), _p(Xf), d(nu_shape), d(nu_rate),
-        d(alpha_a), d(alpha_b), d(tau_true), d(alpha), i(P), i(N), i(M), i(burn),
-        ctypes.byref(rt), i(K))
+    args = [_p(raw["mean"]), _p(raw["var"]), _p(raw["acov"]), _p(raw["hmean"]), _p(raw["hvar"]),
+            raw["flags"].ctypes.data_as(_ip), i(lag), _p(y), _p(Xf), d(nu_shape), d(nu_rate),
+            d(alpha_a), d(alpha_b), d(tau_true), d(alpha), i(P), i(N), i(M), i(burn),
+            ctypes.byref(rt), i(K)]
+    qraw = None
+    if probs is None:
+        L.bridge_reg_logit_chains_summary(*args)
+    else:
+        qraw = _quantile_buffers(P + 3, probs)
+        L.bridge_reg_logit_chains_summary_q(*args, *_quantile_args(qraw, dot_c=True))
     if np.isnan(raw["mean"]).all() and rt.value == 0.0:
         raise RuntimeError(f"{entry}: the call returned no summaries: {_err()}")
-    return _summary_result(raw, P, M, lag, rt.value)
+    out = _summary_result(raw, P, M, lag, rt.value)
+    if qraw is not None:
+        out.update(_quantile_result(qraw))
+    return out
 
 
 def pg_batch(psi, seed, stream=0, t=0):
@@ -1667,6 +1770,19 @@ class ChainBatch:
         raw["flags"] = raw["flags"].astype(np.uint32)
         raw.update(nsamp=nsamp, maxlag=lag, p=self.p)
         return raw
+
+    def quantiles_reset(self):
+        """Enable and zero the pooled quantile sketch for the samples of the summary: after
+        ``summary_reset`` and before the first ``summary_add``, which then feeds it."""
+        _check(library().bb_chains_quantiles_reset(self._h), "bb_chains_quantiles_reset")
+
+    def quantiles(self, probs):
+        """The pooled quantiles once all samples are in: the quantile keys of
+        ``bridge_reg_stb_chains_summary``, Q = p + 3."""
+        raw = _quantile_buffers(self.p + 3, _check_probs(probs, "ChainBatch.quantiles"))
+        _check(library().bb_chains_quantiles_get(self._h, *_quantile_args(raw)),
+               "bb_chains_quantiles_get")
+        return _quantile_result(raw)
 
     def threads(self) -> int:
         """Threads per workgroup of the kernel instance this batch runs."""

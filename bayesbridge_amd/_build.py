@@ -17,9 +17,11 @@ SO_PATH = os.path.join(HERE, "BayesBridge.so")
 OBJ_DIR = os.path.join(HERE, "build")  # per-source objects (kept: tests relink them)
 SOURCES = ["bb_kernels.hip", "bb_ozaki.hip", "bb_tri.hip", "bb_tri_mh.hip", "bb_sparse.hip", "bb_logit.hip", "bb_nid.hip",
            "bb_small.hip", "bb_small_mh.hip", "bb_wide.hip", "bb_logit_chain.hip", "bb_summary.hip",
+           "bb_quantile.hip",
            "bb_engine.cpp", "bb_prims.cpp"]
 HEADERS = ["bb_kernels.h", "bb_sampler.h", "bb_ozaki.h", "bb_sparse.h", "bb_pg.h", "bb_chol4.h",
-           "bb_host.h", "bb_small_body.h", "bb_tri_body.h", "bb_wave.h", "bb_chain_steps.h"]
+           "bb_host.h", "bb_small_body.h", "bb_tri_body.h", "bb_wave.h", "bb_chain_steps.h",
+           "bb_quantile.h"]
 ARCH = os.environ.get("BB_OFFLOAD_ARCH", "gfx950")
 
 

@@ -1714,14 +1714,23 @@ struct Traces {
 
 // The outputs of a .C summary call, K chains of Q = P + 3 parameters (beta, sig2, tau, alpha):
 // mean, var Q x K, acov (L + 1) x Q x K, hmean, hvar 2 x Q x K column-major, flags K.
+// The pooled quantile outputs of a `_q` summary entry (TraceQuantiles::get): probs nprobs,
+// centre Q, zlo, zhi, below, inbin [Q][nprobs], counts [Q][6].
+struct QuantOut {
+    const double *probs;
+    int nprobs;
+    double *centre, *zlo, *zhi, *below, *inbin, *counts;
+};
+
 struct SummaryOut {
     double *mean, *var, *acov, *hmean, *hvar;
     int *flags;
     int maxlag;
+    const QuantOut *quant = nullptr;  // pooled over the chains: the same for every slice
     // chain k's slice
     SummaryOut chain(size_t k, size_t q) const {
         return {mean + k * q, var + k * q, acov + k * q * (maxlag + 1), hmean + 2 * k * q,
-                hvar + 2 * k * q, flags + k, maxlag};
+                hvar + 2 * k * q, flags + k, maxlag, quant};
     }
 };
 
@@ -1912,11 +1921,32 @@ struct bb_chains {
     }
     void summary_reset(int nsamp, int maxlag) {
         if (!summary) summary.reset(new TraceSummary());
+        quant.reset();  // a sketch belongs to one summary: quantiles_reset enables it again
         summary->reset(stream(), K, p + 3, nsamp, maxlag);
     }
     void summary_add(int slot0, int count, int s0) {
         if (!summary) throw HipError("summary: add before reset");
         summary->add(stream(), summary_ring(), slot0, count, s0);
+        if (quant) quant->add(stream(), summary_ring(), K, slot0, count, s0);
+    }
+    // The optional pooled quantile sketch (bb_quantile.hip) of the samples the summary takes:
+    // enabled after summary_reset and before the first summary_add, fed by summary_add.
+    std::unique_ptr<TraceQuantiles> quant;
+    void quantiles_reset() {
+        if (!summary) throw HipError("quantiles: reset after summary_reset");
+        if (summary->next != 0) throw HipError("quantiles: reset before the first summary_add");
+        if (!quant) quant.reset(new TraceQuantiles());
+        try {
+            quant->reset(stream(), K, p + 3, summary->M);
+        } catch (...) {
+            quant.reset();
+            throw;
+        }
+    }
+    void quantiles_get(const double *probs, int nprobs, double *centre, double *zlo, double *zhi,
+                       double *below, double *inbin, double *counts) {
+        if (!quant) throw HipError("quantiles: get before reset");
+        quant->get(stream(), probs, nprobs, centre, zlo, zhi, below, inbin, counts);
     }
     // the summaries and every chain's error word (any output may be null)
     void summary_get(double *mean, double *var, double *acov, double *hmean, double *hvar,
@@ -2599,6 +2629,18 @@ int bb_chains_summary_get(bb_chains *b, double *mean, double *var, double *acov,
                           double *hvar, int *flags) {
     return guarded(b->proto->cfg.device,
                    [&] { b->summary_get(mean, var, acov, hmean, hvar, flags); });
+}
+
+int bb_chains_quantiles_reset(bb_chains *b) {
+    return guarded(b->proto->cfg.device, [&] { b->quantiles_reset(); });
+}
+
+int bb_chains_quantiles_get(bb_chains *b, const double *probs, int nprobs, double *centre,
+                            double *zlo, double *zhi, double *below, double *inbin,
+                            double *counts) {
+    return guarded(b->proto->cfg.device, [&] {
+        b->quantiles_get(probs, nprobs, centre, zlo, zhi, below, inbin, counts);
+    });
 }
 
 // ~0u when the flags cannot be read; bb_last_error then says why and is empty otherwise, which
@@ -3287,6 +3329,7 @@ Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const doubl
     g_last_capacity = ch->cap;
     ChainsRun run{raw, ch->cap};
     if (sum && bb_chains_summary_reset(raw, m, sum->maxlag) != 0) return OUT_ERROR;
+    if (sum && sum->quant && bb_chains_quantiles_reset(raw) != 0) return OUT_ERROR;
     const Outcome o = drive_schedule(
         run, ch->block(), kd.nburn, kd.t_base, m, b, runtime,
         [&](int slot0, int count, int s0) {
@@ -3308,6 +3351,10 @@ Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const doubl
     if (sum && o == OUT_OK &&
         bb_chains_summary_get(raw, sum->mean, sum->var, sum->acov, sum->hmean, sum->hvar,
                               sum->flags) != 0)
+        return OUT_ERROR;
+    if (const QuantOut *q = sum ? sum->quant : nullptr; q && o == OUT_OK &&
+        bb_chains_quantiles_get(raw, q->probs, q->nprobs, q->centre, q->zlo, q->zhi, q->below,
+                                q->inbin, q->counts) != 0)
         return OUT_ERROR;
     return o;
 }
@@ -3343,8 +3390,11 @@ Outcome chains_call(const CallKind &kd, const bb_config &c, int K, const double 
 // One chain of a summary call on a single engine: its ring ([slot][p], tr_sig2 / tr_tau /
 // tr_alpha) is reduced by the chain batch's kernel with one chain.  An interrupted or failed
 // run leaves the outputs as they were.
+// With `tq` the chain's samples also go to the call's pooled quantile sketch, which the first
+// chain sizes for all `nchains` (its first kept draw is the centre).
 Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const double *yp,
-                           const double *Xp, const SummaryOut &out, double *runtime) {
+                           const double *Xp, const SummaryOut &out, double *runtime,
+                           TraceQuantiles *tq = nullptr, int nchains = 1) {
     const int m = c.trace_capacity, n = c.n;
     print_banner(kd.title, c, b, m);
     g_last_interrupted = 0;
@@ -3369,6 +3419,7 @@ Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const 
                                .alpha = e->tr_alpha, .p = e->p_loc, .cap = ch.cap};
         o = (Outcome)guarded(e->cfg.device, [&] {
             ts.reset(e->stream, 1, c.p + 3, m, out.maxlag);
+            if (tq && !tq->ready()) tq->reset(e->stream, nchains, c.p + 3, m);
             return (int)OUT_OK;
         });
         if (o != OUT_OK) o = OUT_ERROR;
@@ -3378,6 +3429,7 @@ Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const 
                 [&](int slot0, int count, int s0) {
                     HIPCHECK(hipSetDevice(e->cfg.device));
                     ts.add(e->stream, ring, slot0, count, s0);
+                    if (tq) tq->add(e->stream, ring, 1, slot0, count, s0);
                     return 0;
                 },
                 [&] {
@@ -3423,13 +3475,26 @@ Outcome chains_summary_call(const char *entry, const CallKind &kd, const bb_conf
         print_abort("%s", g_last_error.c_str());
         return OUT_ERROR;
     }
+    // one sketch for the whole call: every chain's stream is drained (the summary's get)
+    // before the next chain starts, so the adds of the K engines never overlap
+    TraceQuantiles tq;
     for (int k = 0; k < K; ++k) {
         bb_config ck = c;
         ck.stream = c.stream + (uint64_t)k;
         double rt = 0.0;
-        const Outcome o = summary_chain_call(kd, ck, b, yp, Xp, out.chain(k, c.p + 3), &rt);
+        const Outcome o = summary_chain_call(kd, ck, b, yp, Xp, out.chain(k, c.p + 3), &rt,
+                                             out.quant ? &tq : nullptr, K);
         *runtime += rt;
         if (o != OUT_OK) return o;
+    }
+    if (const QuantOut *q = out.quant) {
+        if (guarded(tq.device, [&] {
+                tq.get(0, q->probs, q->nprobs, q->centre, q->zlo, q->zhi, q->below, q->inbin,
+                       q->counts);
+            }) != 0) {
+            print_abort("%s", g_last_error.c_str());
+            return OUT_ERROR;
+        }
     }
     return OUT_OK;
 }
@@ -3526,6 +3591,20 @@ bool summary_args_ok(const char *entry, int nsamp, int maxlag) {
     const char *why = TraceSummary::refusal(nsamp, maxlag);
     if (!why) return true;
     set_error("%s: %s (got maxlag %d, %d samples)", entry, why, maxlag, nsamp);
+    printf("Error: %s\n", g_last_error.c_str());
+    fflush(stdout);
+    return false;
+}
+
+// a _q summary entry's probabilities and pooled sample count, checked like nchains (q null:
+// the entry without quantiles)
+bool quant_args_ok(const char *entry, const QuantOut *q, int nchains, int nsamp) {
+    if (!q) return true;
+    const char *why = TraceQuantiles::probs_refusal(q->probs, q->nprobs);
+    if (!why) why = TraceQuantiles::refusal(nchains, nsamp);
+    if (!why) return true;
+    set_error("%s: %s (got %d probabilities, %d chains of %d samples)", entry, why, q->nprobs,
+              nchains, nsamp);
     printf("Error: %s\n", g_last_error.c_str());
     fflush(stdout);
     return false;
@@ -3691,6 +3770,29 @@ void bridge_reg_stable_chains(double *betap, double *lambdap, double *sig2p, dou
         reraise_interrupt();
 }
 
+// the body of bridge_reg_stable_chains_summary and, with q, of its _q form
+static void stable_chains_summary(const char *entry, const QuantOut *q, double *meanp,
+                                  double *varp, double *acovp, double *hmeanp, double *hvarp,
+                                  int *flagsp, const int *maxlag, const double *yp,
+                                  const double *Xp, const double *sig2_shape,
+                                  const double *sig2_scale, const double *nu_shape,
+                                  const double *nu_rate, const double *alpha_a,
+                                  const double *alpha_b, const double *true_sig2,
+                                  const double *true_tau, const double *true_alpha, const int *P,
+                                  const int *N, const int *M, const int *burn, double *runtime,
+                                  const int *ortho, const int *nchains) {
+    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag) ||
+        !quant_args_ok(entry, q, *nchains, *M))
+        return;
+    const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                           alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                           ortho, *nchains);
+    if (chains_summary_call(entry, stable_kind(*burn), c, *nchains, yp, Xp, *burn,
+                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag, q},
+                            runtime) == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
 void bridge_reg_stable_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
                                       double *hvarp, int *flagsp, const int *maxlag,
                                       const double *yp, const double *Xp,
@@ -3701,15 +3803,26 @@ void bridge_reg_stable_chains_summary(double *meanp, double *varp, double *acovp
                                       const double *true_alpha, const int *P, const int *N,
                                       const int *M, const int *burn, double *runtime,
                                       const int *ortho, const int *nchains) {
-    const char *entry = "bridge_reg_stable_chains_summary";
-    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag)) return;
-    const bb_config c = stable_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
-                                           alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
-                                           ortho, *nchains);
-    if (chains_summary_call(entry, stable_kind(*burn), c, *nchains, yp, Xp, *burn,
-                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag},
-                            runtime) == OUT_INTERRUPTED)
-        reraise_interrupt();
+    stable_chains_summary("bridge_reg_stable_chains_summary", nullptr, meanp, varp, acovp, hmeanp,
+                          hvarp, flagsp, maxlag, yp, Xp, sig2_shape, sig2_scale, nu_shape,
+                          nu_rate, alpha_a, alpha_b, true_sig2, true_tau, true_alpha, P, N, M,
+                          burn, runtime, ortho, nchains);
+}
+
+void bridge_reg_stable_chains_summary_q(
+    double *meanp, double *varp, double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+    const int *maxlag, const double *yp, const double *Xp, const double *sig2_shape,
+    const double *sig2_scale, const double *nu_shape, const double *nu_rate,
+    const double *alpha_a, const double *alpha_b, const double *true_sig2,
+    const double *true_tau, const double *true_alpha, const int *P, const int *N, const int *M,
+    const int *burn, double *runtime, const int *ortho, const int *nchains, const double *probs,
+    const int *nprobs, double *centrep, double *zlop, double *zhip, double *belowp,
+    double *inbinp, double *countsp) {
+    const QuantOut q{probs, *nprobs, centrep, zlop, zhip, belowp, inbinp, countsp};
+    stable_chains_summary("bridge_reg_stable_chains_summary_q", &q, meanp, varp, acovp, hmeanp,
+                          hvarp, flagsp, maxlag, yp, Xp, sig2_shape, sig2_scale, nu_shape,
+                          nu_rate, alpha_a, alpha_b, true_sig2, true_tau, true_alpha, P, N, M,
+                          burn, runtime, ortho, nchains);
 }
 
 void bridge_reg_stable_csc(double *betap, double *lambdap, double *sig2p, double *taup,
@@ -3759,6 +3872,26 @@ void bridge_reg_logit_chains(double *betap, double *lambdap, double *taup, doubl
         reraise_interrupt();
 }
 
+// the body of bridge_reg_logit_chains_summary and, with q, of its _q form
+static void logit_chains_summary(const char *entry, const QuantOut *q, double *meanp, double *varp,
+                                 double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+                                 const int *maxlag, const double *yp, const double *Xp,
+                                 const double *nu_shape, const double *nu_rate,
+                                 const double *alpha_a, const double *alpha_b,
+                                 const double *true_tau, const double *true_alpha, const int *P,
+                                 const int *N, const int *M, const int *burn, double *runtime,
+                                 const int *nchains) {
+    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag) ||
+        !quant_args_ok(entry, q, *nchains, *M) || !logit_y_ok(entry, yp, *N))
+        return;
+    const bb_config c = logit_chains_config(nu_shape, nu_rate, alpha_a, alpha_b, true_tau,
+                                            true_alpha, *P, *N, *M, *nchains);
+    if (chains_summary_call(entry, logit_kind(*burn), c, *nchains, yp, Xp, *burn,
+                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag, q},
+                            runtime) == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
 void bridge_reg_logit_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
                                      double *hvarp, int *flagsp, const int *maxlag,
                                      const double *yp, const double *Xp, const double *nu_shape,
@@ -3767,16 +3900,22 @@ void bridge_reg_logit_chains_summary(double *meanp, double *varp, double *acovp,
                                      const double *true_alpha, const int *P, const int *N,
                                      const int *M, const int *burn, double *runtime,
                                      const int *nchains) {
-    const char *entry = "bridge_reg_logit_chains_summary";
-    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag) ||
-        !logit_y_ok(entry, yp, *N))
-        return;
-    const bb_config c = logit_chains_config(nu_shape, nu_rate, alpha_a, alpha_b, true_tau,
-                                            true_alpha, *P, *N, *M, *nchains);
-    if (chains_summary_call(entry, logit_kind(*burn), c, *nchains, yp, Xp, *burn,
-                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag},
-                            runtime) == OUT_INTERRUPTED)
-        reraise_interrupt();
+    logit_chains_summary("bridge_reg_logit_chains_summary", nullptr, meanp, varp, acovp, hmeanp,
+                         hvarp, flagsp, maxlag, yp, Xp, nu_shape, nu_rate, alpha_a, alpha_b,
+                         true_tau, true_alpha, P, N, M, burn, runtime, nchains);
+}
+
+void bridge_reg_logit_chains_summary_q(
+    double *meanp, double *varp, double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+    const int *maxlag, const double *yp, const double *Xp, const double *nu_shape,
+    const double *nu_rate, const double *alpha_a, const double *alpha_b, const double *true_tau,
+    const double *true_alpha, const int *P, const int *N, const int *M, const int *burn,
+    double *runtime, const int *nchains, const double *probs, const int *nprobs, double *centrep,
+    double *zlop, double *zhip, double *belowp, double *inbinp, double *countsp) {
+    const QuantOut q{probs, *nprobs, centrep, zlop, zhip, belowp, inbinp, countsp};
+    logit_chains_summary("bridge_reg_logit_chains_summary_q", &q, meanp, varp, acovp, hmeanp,
+                         hvarp, flagsp, maxlag, yp, Xp, nu_shape, nu_rate, alpha_a, alpha_b,
+                         true_tau, true_alpha, P, N, M, burn, runtime, nchains);
 }
 
 void bridge_regression(double *betap, double *up, double *omegap, double *shapep,
@@ -3816,6 +3955,29 @@ void bridge_regression_chains(double *betap, double *up, double *omegap, double 
         reraise_interrupt();
 }
 
+// the body of bridge_regression_chains_summary and, with q, of its _q form
+static void tri_chains_summary(const char *entry, const QuantOut *q, double *meanp, double *varp,
+                               double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+                               const int *maxlag, const double *yp, const double *Xp,
+                               const double *sig2_shape, const double *sig2_scale,
+                               const double *nu_shape, const double *nu_rate,
+                               const double *alpha_a, const double *alpha_b,
+                               const double *true_sig2, const double *true_tau,
+                               const double *true_alpha, const int *P, const int *N, const int *M,
+                               const int *burn, double *runtime, const int *ortho,
+                               const int *betaburn, const int *nchains) {
+    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag) ||
+        !quant_args_ok(entry, q, *nchains, *M))
+        return;
+    const bb_config c = tri_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
+                                        alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
+                                        ortho, betaburn, *nchains);
+    if (chains_summary_call(entry, tri_kind(*burn), c, *nchains, yp, Xp, *burn,
+                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag, q},
+                            runtime) == OUT_INTERRUPTED)
+        reraise_interrupt();
+}
+
 void bridge_regression_chains_summary(double *meanp, double *varp, double *acovp, double *hmeanp,
                                       double *hvarp, int *flagsp, const int *maxlag,
                                       const double *yp, const double *Xp,
@@ -3828,15 +3990,27 @@ void bridge_regression_chains_summary(double *meanp, double *varp, double *acovp
                                       const int *ortho, const int *betaburn, const int *use_hmc,
                                       const int *nchains) {
     (void)use_hmc;
-    const char *entry = "bridge_regression_chains_summary";
-    if (!nchains_ok(entry, *nchains) || !summary_args_ok(entry, *M, *maxlag)) return;
-    const bb_config c = tri_call_config(sig2_shape, sig2_scale, nu_shape, nu_rate, alpha_a,
-                                        alpha_b, true_sig2, true_tau, true_alpha, *P, *N, *M,
-                                        ortho, betaburn, *nchains);
-    if (chains_summary_call(entry, tri_kind(*burn), c, *nchains, yp, Xp, *burn,
-                            {meanp, varp, acovp, hmeanp, hvarp, flagsp, *maxlag},
-                            runtime) == OUT_INTERRUPTED)
-        reraise_interrupt();
+    tri_chains_summary("bridge_regression_chains_summary", nullptr, meanp, varp, acovp, hmeanp,
+                       hvarp, flagsp, maxlag, yp, Xp, sig2_shape, sig2_scale, nu_shape, nu_rate,
+                       alpha_a, alpha_b, true_sig2, true_tau, true_alpha, P, N, M, burn, runtime,
+                       ortho, betaburn, nchains);
+}
+
+void bridge_regression_chains_summary_q(
+    double *meanp, double *varp, double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+    const int *maxlag, const double *yp, const double *Xp, const double *sig2_shape,
+    const double *sig2_scale, const double *nu_shape, const double *nu_rate,
+    const double *alpha_a, const double *alpha_b, const double *true_sig2,
+    const double *true_tau, const double *true_alpha, const int *P, const int *N, const int *M,
+    const int *burn, double *runtime, const int *ortho, const int *betaburn, const int *use_hmc,
+    const int *nchains, const double *probs, const int *nprobs, double *centrep, double *zlop,
+    double *zhip, double *belowp, double *inbinp, double *countsp) {
+    (void)use_hmc;
+    const QuantOut q{probs, *nprobs, centrep, zlop, zhip, belowp, inbinp, countsp};
+    tri_chains_summary("bridge_regression_chains_summary_q", &q, meanp, varp, acovp, hmeanp,
+                       hvarp, flagsp, maxlag, yp, Xp, sig2_shape, sig2_scale, nu_shape, nu_rate,
+                       alpha_a, alpha_b, true_sig2, true_tau, true_alpha, P, N, M, burn, runtime,
+                       ortho, betaburn, nchains);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "bb_kernels.h"
+#include "bb_quantile.h"
 #include "bb_sparse.h"
 
 #pragma GCC visibility push(hidden)
@@ -224,6 +225,120 @@ struct TraceSummary {
         fetch(acov, da, kq * (L + 1));
         fetch(hmean, dhm, 2 * kq);
         fetch(hvar, dhv, 2 * kq);
+    }
+};
+
+// The pooled order-statistic sketch of K chains' trace rings (bb_quantile.hip; the bins:
+// bb_quantile.h): reset(), then every chain's M samples through add() as the rings fill -- all
+// chains of a batch at once, or one chain after another through single-chain rings -- then
+// get() for any probabilities.  One histogram and three counters per parameter, pooled over
+// the chains; the centre is the first sample of the first add().  Enqueued on the caller's
+// stream like TraceSummary; integer counts, so the order of the adds changes nothing.
+struct TraceQuantiles {
+    int K = 0, Q = 0, M = 0;
+    int device = 0;                // the device current at reset(): where the sketch lives
+    unsigned long long added = 0;  // samples added so far, over all chains
+    bool centred = false;
+    unsigned int *hist = nullptr;  // [Q][kQuantBins], then the counters [Q][kQuantCounters]
+    double *centre = nullptr;      // [Q]
+    size_t hist_count = 0, centre_count = 0;
+    TraceQuantiles() = default;
+    TraceQuantiles(const TraceQuantiles &) = delete;
+    TraceQuantiles &operator=(const TraceQuantiles &) = delete;
+    ~TraceQuantiles() {
+        (void)hipFree(hist);
+        (void)hipFree(centre);
+    }
+    unsigned int *counters() const { return hist + (size_t)Q * kQuantBins; }
+    // why K chains of nsamp samples cannot be pooled, or nullptr (the counts are 32-bit)
+    static const char *refusal(int nchains, int nsamp) {
+        if (nchains < 1 || nsamp < 1) return "no chains or no samples";
+        if ((unsigned long long)nchains * (unsigned long long)nsamp >= (1ull << 32))
+            return "nchains x nsamp must be below 2^32 (the sketch counts in 32 bits)";
+        return nullptr;
+    }
+    // why these probabilities cannot be selected, or nullptr
+    static const char *probs_refusal(const double *probs, int nprobs) {
+        if (nprobs < 1) return "at least one probability is needed";
+        if (nprobs > kQuantMaxProbs) return "at most 64 probabilities per call";
+        for (int j = 0; j < nprobs; ++j)
+            if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return "every probability must be in [0, 1]";
+        return nullptr;
+    }
+    bool ready() const { return hist != nullptr && K > 0; }
+    // sized for K chains of Q parameters and M samples each, and zeroed
+    void reset(hipStream_t s, int K_, int Q_, int M_) {
+        if (const char *why = refusal(K_, M_)) throw HipError(std::string("quantiles: ") + why);
+        if (Q_ < 1) throw HipError("quantiles: no parameters");
+        const size_t nh = (size_t)Q_ * (kQuantBins + kQuantCounters);
+        if (hist_count != nh || centre_count != (size_t)Q_) {
+            HIPCHECK(hipStreamSynchronize(s));
+            (void)hipFree(hist);
+            (void)hipFree(centre);
+            hist = nullptr, centre = nullptr, hist_count = centre_count = 0;
+            HIPCHECK(hipMalloc((void **)&hist, nh * sizeof(unsigned int)));
+            hist_count = nh;
+            HIPCHECK(hipMalloc((void **)&centre, (size_t)Q_ * sizeof(double)));
+            centre_count = (size_t)Q_;
+        }
+        K = K_, Q = Q_, M = M_, added = 0, centred = false;
+        HIPCHECK(hipGetDevice(&device));
+        HIPCHECK(hipMemsetAsync(hist, 0, nh * sizeof(unsigned int), s));
+        HIPCHECK(hipMemsetAsync(centre, 0, (size_t)Q_ * sizeof(double), s));
+    }
+    // ring slots [slot0, slot0 + count) (wrapping at ring.cap) of each of the ring's `chains`
+    // chains; the very first add starts at a chain's sample 0 and fixes the centre
+    void add(hipStream_t s, const SummaryRing &ring, int chains, int slot0, int count, int s0) {
+        if (!ready()) throw HipError("quantiles: add before reset");
+        if (ring.params() != Q) throw HipError("quantiles: the rings hold another parameter count");
+        if (slot0 < 0 || count < 0 || chains < 1)
+            throw HipError("quantiles: slot0 and count must be >= 0");
+        const unsigned long long total = (unsigned long long)K * M;
+        if ((unsigned long long)chains * count > total - added)
+            throw HipError("quantiles: more samples than the sketch was sized for");
+        if (count == 0) return;
+        if (!centred) {
+            if (s0 != 0) throw HipError("quantiles: the first samples added must start at 0");
+            launch_quantile_centre(s, ring, slot0 % ring.cap, centre);
+            centred = true;
+        }
+        ring_runs(slot0, count, ring.cap, [&](int, int slot, int run) {
+            launch_trace_hist(s, ring, chains, slot, run, centre, hist, counters());
+        });
+        HIPCHECK(hipGetLastError());
+        added += (unsigned long long)chains * count;
+    }
+    // The selection once every sample is in: centre [Q], zlo, zhi, below, inbin [Q][nprobs],
+    // counts [Q][6] (any may be null).  Waits for the stream.
+    void get(hipStream_t s, const double *probs, int nprobs, double *centre_out, double *zlo,
+             double *zhi, double *below, double *inbin, double *counts) {
+        const unsigned long long total = (unsigned long long)K * M;
+        if (!ready() || added != total) {
+            char b[128];
+            snprintf(b, sizeof(b), "quantiles: %llu of %llu samples added", ready() ? added : 0ull,
+                     ready() ? total : 0ull);
+            throw HipError(b);
+        }
+        if (const char *why = probs_refusal(probs, nprobs))
+            throw HipError(std::string("quantiles: ") + why);
+        Scratch dev;
+        const size_t qn = (size_t)Q * nprobs;
+        double *dp = dev.alloc<double>(nprobs), *out = dev.alloc<double>(4 * qn + 6 * (size_t)Q);
+        HIPCHECK(hipMemcpyAsync(dp, probs, (size_t)nprobs * sizeof(double), hipMemcpyHostToDevice,
+                                s));
+        launch_quantile_select(s, hist, counters(), Q, total, dp, nprobs, out, out + qn,
+                               out + 2 * qn, out + 3 * qn, out + 4 * qn);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(s));
+        auto fetch = [&](double *dst, const double *src, size_t n) {
+            if (dst) HIPCHECK(hipMemcpy(dst, src, n * sizeof(double), hipMemcpyDeviceToHost));
+        };
+        fetch(centre_out, centre, (size_t)Q);
+        fetch(zlo, out, qn);
+        fetch(zhi, out + qn, qn);
+        fetch(below, out + 2 * qn, qn);
+        fetch(inbin, out + 3 * qn, qn);
+        fetch(counts, out + 4 * qn, 6 * (size_t)Q);
     }
 };
 

@@ -281,6 +281,54 @@ int bb_trace_summary(const double *x, int K, int M, int Q, int maxlag, int chunk
     });
 }
 
+int bb_quantile_bin(double z, int *bin, double *lo, double *hi) {
+    const int b = quantile_bin(z);
+    if (bin) *bin = b;
+    double e0 = __builtin_nan(""), e1 = e0;
+    if (b >= 0) quantile_bin_edges(b, &e0, &e1);
+    if (lo) *lo = e0;
+    if (hi) *hi = e1;
+    return b >= 0 ? 0 : -1;
+}
+
+int bb_trace_quantiles(const double *x, int K, int M, int Q, int chunk, const double *probs,
+                       int nprobs, double *centre, double *zlo, double *zhi, double *below,
+                       double *inbin, double *counts) {
+    if (K < 1 || M < 1 || Q < 1 || chunk < 1) {
+        set_error("bb_trace_quantiles: K, M, Q and chunk must be at least 1");
+        return -1;
+    }
+    const char *why = TraceQuantiles::probs_refusal(probs, nprobs);
+    if (!why) why = TraceQuantiles::refusal(K, M);
+    if (why) {
+        set_error("bb_trace_quantiles: %s (got %d probabilities, %d chains of %d samples)", why,
+                  nprobs, K, M);
+        return -1;
+    }
+    return guarded(g_device, [&] {
+        Scratch dev;
+        // the rings as bb_trace_summary lays them out
+        const int P = Q > 3 ? Q - 3 : Q;
+        const size_t slots = (size_t)K * M;
+        double *db = dev.alloc<double>(slots * P), *ds = nullptr;
+        HIPCHECK(hipMemcpy2D(db, (size_t)P * sizeof(double), x, (size_t)Q * sizeof(double),
+                             (size_t)P * sizeof(double), slots, hipMemcpyHostToDevice));
+        if (P < Q) {
+            ds = dev.alloc<double>(3 * slots);
+            for (int j = 0; j < 3; ++j)
+                HIPCHECK(hipMemcpy2D(ds + j * slots, sizeof(double), x + P + j,
+                                     (size_t)Q * sizeof(double), sizeof(double), slots,
+                                     hipMemcpyHostToDevice));
+        }
+        SummaryRing ring{.beta = db, .p = P, .cap = M};
+        if (ds) ring.sig2 = ds, ring.tau = ds + slots, ring.alpha = ds + 2 * slots;
+        TraceQuantiles tq;
+        tq.reset(0, K, Q, M);
+        for (int s = 0; s < M; s += chunk) tq.add(0, ring, K, s, std::min(chunk, M - s), s);
+        tq.get(0, probs, nprobs, centre, zlo, zhi, below, inbin, counts);
+    });
+}
+
 int bb_gram_ozaki(double *C, const double *Yh, const double *wh, int n, int k) {
     return guarded(g_device, [&] {
         Scratch dev;

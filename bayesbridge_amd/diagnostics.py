@@ -12,7 +12,8 @@ from __future__ import annotations
 import numpy as np
 
 __all__ = ["effective_size", "sum_stat", "rhat", "sum_stat_chains", "effective_size_from_acov",
-           "rhat_from_moments", "sum_stat_from_summary", "default_maxlag"]
+           "rhat_from_moments", "sum_stat_from_summary", "default_maxlag",
+           "quantiles_from_bins"]
 
 
 def default_maxlag(n: int) -> int:
@@ -205,3 +206,30 @@ def sum_stat_from_summary(summary, runtime: float):
             "ess_summary": (float(ess.min()), float(np.median(ess)), float(ess.max())),
             "esr_summary": (float(esr.min()), float(np.median(esr)), float(esr.max())),
             "runtime": runtime, "chains": K}
+
+
+def quantiles_from_bins(probs, centre, zlo, zhi, below, inbin, counts):
+    """Point estimates of pooled quantiles from the device's bin selection (the quantile keys
+    of ``bridge_reg_stb_chains_summary``): for parameter q and probability pi, with N =
+    counts[q, 0] and the rank k = min(N, max(1, ceil(pi N))) (R's type-1 quantile), the k-th
+    smallest draw lies in [centre + zlo, centre + zhi], a bin that holds ``inbin`` draws above
+    ``below`` lower ones; the estimate interpolates by rank inside it,
+    centre + zlo + (k - below - 1/2) / inbin (zhi - zlo), and is the finite edge in an overflow
+    bin.  Returns quantile, quantile_lo, quantile_hi (Q x nprobs; NaN where N = 0) and
+    prob_pos, prob_neg (Q: the shares of draws > 0 and < 0 among the N that are not NaN)."""
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    centre = np.asarray(centre, dtype=np.float64)[:, None]
+    zlo, zhi = np.asarray(zlo, dtype=np.float64), np.asarray(zhi, dtype=np.float64)
+    below, inbin = np.asarray(below, dtype=np.float64), np.asarray(inbin, dtype=np.float64)
+    counts = np.asarray(counts, dtype=np.float64)
+    N = counts[:, :1]
+    k = np.minimum(N, np.maximum(1.0, np.ceil(probs[None, :] * N)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        frac = (k - below - 0.5) / inbin
+        est = zlo + frac * (zhi - zlo)
+        est = np.where(np.isinf(zlo), zhi, np.where(np.isinf(zhi), zlo, est))
+        est = np.where(N > 0, est, np.nan)
+        n1 = np.where(counts[:, 0] > 0, counts[:, 0], np.nan)
+        out = {"quantile": centre + est, "quantile_lo": centre + zlo, "quantile_hi": centre + zhi,
+               "prob_neg": counts[:, 2] / n1, "prob_pos": counts[:, 3] / n1}
+    return out

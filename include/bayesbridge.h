@@ -487,6 +487,76 @@ void bridge_regression_chains_summary(double *meanp, double *varp, double *acovp
                                       const int *nchains);
 
 /*
+ * Pooled credible intervals from the summary calls: an order-statistic sketch over ALL K chains
+ * of a batch, built on the device behind the sweeps like the moment summary.
+ * Per parameter q (beta_1..beta_P, sig2, tau, alpha) every sample x is binned as z = x - c_q,
+ * c_q = sample 0 of chain 0, into a histogram of 65539 integer counts keyed on the bits of z:
+ * with a the bits of |z|, e = a >> 52 and m = (a >> 44) & 0xff, ordinary bin
+ * r = (e - 959) 256 + m for 2^-64 <= |z| < 2^64 (index 32768 - r for z < 0, 32770 + r for
+ * z > 0), the zero bin (index 32769) below that, an overflow bin per sign (indices 0 and 65538)
+ * above; NaN is counted, not binned.  Positive bin r is [lo, hi) with lo's bits
+ * ((r >> 8) + 959) << 52 | (r & 255) << 44 and hi's those plus 1 << 44: a bin is at most
+ * 2^-8 |z| wide.  The result does not depend on the ring capacity, on ring wrap, on the split
+ * into launches or on the grid.
+ *
+ * For probability pi, with N = K M - NaNs, the rank is k = min(N, max(1, ceil(pi N))) (R's
+ * type-1 quantile).  Outputs, C order: centre [Q]; zlo, zhi [Q][nprobs] the edges of the bin
+ * that holds the k-th smallest z (so centre + zlo <= that order statistic <= centre + zhi up
+ * to the rounding of the sum); below, inbin [Q][nprobs] the count in lower bins and in that
+ * bin (below < k <= below + inbin); counts [Q][6]: N, NaN, x < 0, x > 0 (of the uncentred
+ * samples), zero-bin, overflow.  With N = 0 zlo, zhi, below and inbin are NaN.  1 <= nprobs <=
+ * 64, every probability in [0, 1], K M < 2^32; an output pointer of the step API may be NULL.
+ *
+ * bb_chains_quantiles_reset enables and zeroes the sketch of a batch for the samples of its
+ * summary (after bb_chains_summary_reset, before the first bb_chains_summary_add, which then
+ * feeds it; the next bb_chains_summary_reset drops it); bb_chains_quantiles_get selects once
+ * every sample is in, any number of times.
+ */
+int bb_chains_quantiles_reset(bb_chains *b);
+int bb_chains_quantiles_get(bb_chains *b, const double *probs, int nprobs, double *centre,
+                            double *zlo, double *zhi, double *below, double *inbin,
+                            double *counts);
+
+/* The bin of z under the scheme above and its edges (host code; bin -1, NaN edges and return
+ * -1 for a NaN; any pointer may be NULL). */
+int bb_quantile_bin(double z, int *bin, double *lo, double *hi);
+
+/*
+ * The three summary entries with pooled quantiles: the summary entry's arguments, then
+ * probs (nprobs doubles), nprobs, and the outputs centre, zlo, zhi, below, inbin, counts as
+ * above (R: nprobs x Q and 6 x Q column-major).  The chains, the moment outputs and flags are
+ * those of the entry without _q.  Where the chains run one after another (no batch for the
+ * design) one sketch pools all K, centred at chain 0's first kept draw.  A refused probs
+ * (count outside [1, 64], a value outside [0, 1] or NaN) or K M >= 2^32 prints an error
+ * (bb_last_error) and returns before a key is taken or an output is written.
+ */
+void bridge_reg_stable_chains_summary_q(
+    double *meanp, double *varp, double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+    const int *maxlag, const double *yp, const double *Xp, const double *sig2_shape,
+    const double *sig2_scale, const double *nu_shape, const double *nu_rate,
+    const double *alpha_a, const double *alpha_b, const double *true_sig2,
+    const double *true_tau, const double *true_alpha, const int *P, const int *N, const int *M,
+    const int *burn, double *runtime, const int *ortho, const int *nchains, const double *probs,
+    const int *nprobs, double *centrep, double *zlop, double *zhip, double *belowp,
+    double *inbinp, double *countsp);
+void bridge_reg_logit_chains_summary_q(
+    double *meanp, double *varp, double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+    const int *maxlag, const double *yp, const double *Xp, const double *nu_shape,
+    const double *nu_rate, const double *alpha_a, const double *alpha_b, const double *true_tau,
+    const double *true_alpha, const int *P, const int *N, const int *M, const int *burn,
+    double *runtime, const int *nchains, const double *probs, const int *nprobs, double *centrep,
+    double *zlop, double *zhip, double *belowp, double *inbinp, double *countsp);
+void bridge_regression_chains_summary_q(
+    double *meanp, double *varp, double *acovp, double *hmeanp, double *hvarp, int *flagsp,
+    const int *maxlag, const double *yp, const double *Xp, const double *sig2_shape,
+    const double *sig2_scale, const double *nu_shape, const double *nu_rate,
+    const double *alpha_a, const double *alpha_b, const double *true_sig2,
+    const double *true_tau, const double *true_alpha, const int *P, const int *N, const int *M,
+    const int *burn, double *runtime, const int *ortho, const int *betaburn, const int *use_hmc,
+    const int *nchains, const double *probs, const int *nprobs, double *centrep, double *zlop,
+    double *zhip, double *belowp, double *inbinp, double *countsp);
+
+/*
  * Shard group: `count` engines with cfg.rank = 0..count-1 and cfg.world = count, each
  * holding a column shard of one p > n chain.  Two kinds share the type:
  *   - bb_group_create: every member on ONE device, driven by one host thread, the per-sweep
@@ -810,6 +880,13 @@ int bb_gram(double *C, const double *Y, const double *w, int n, int k);
  * Outputs as bb_chains_summary_get. */
 int bb_trace_summary(const double *x, int K, int M, int Q, int maxlag, int chunk, double *mean,
                      double *var, double *acov, double *hmean, double *hvar);
+
+/* The quantile-sketch kernels alone (see bb_chains_quantiles_*): x as for bb_trace_summary,
+ * pooled over the K chains and accumulated `chunk` samples at a time.  Outputs as
+ * bb_chains_quantiles_get. */
+int bb_trace_quantiles(const double *x, int K, int M, int Q, int chunk, const double *probs,
+                       int nprobs, double *centre, double *zlo, double *zhi, double *below,
+                       double *inbin, double *counts);
 
 /* Microbenchmark of the Ozaki int8 GEMM alone on random residues (n x k, nsplit K splits, 0 =
  * automatic); dbg != 0 selects timing ablations (results then meaningless), except dbg = 999

@@ -21,6 +21,13 @@ call of the same build at K = CUs and 4 CUs into profiles/chains_summary_{c1,db}
 call, the trace call, the kernel-only rate, and the share of the summary call's runtime that
 k_trace_summary takes (timed alone on a full ring of a ChainBatch, scaled to the call).
 
+--summary --quantiles measures the summary call with pooled quantiles (probs = 0.025, 0.5,
+0.975: the sketch of bb_quantile.hip built behind the sweeps) against the summary call without
+them and the trace call of the same build, alternated within each round at K = CUs and 4 CUs,
+into profiles/chains_summary_quantiles_{c1,db}.json, with the time k_trace_hist takes for the
+call's samples (a full ring added with the sketch enabled less the same add without it) and
+its share of the call.
+
 --alpha measures alpha unknown (alpha = 0, sampled by MH) with the fused kernels sampling it
 (bb_set_tuning key 26, bb_small_mh.hip) at K = 1, 256 and 1024 into
 profiles/chains_alpha_{c1,db}.json: alternated within each round, the single call with the key
@@ -60,6 +67,7 @@ median over rounds is reported with the min and max beside it.
                                                           # checkout at DIR (A/B with a parent)
   python tools/bench_chains.py --method tri [--mode single --tree DIR]
   python tools/bench_chains.py --summary [--method tri] [--designs c1]
+  python tools/bench_chains.py --summary --quantiles [--designs c1]
   python tools/bench_chains.py --wide [--designs dbi]
   python tools/bench_chains.py --alpha --mode single --tree DIR --nsamp 100 --burn 50 > FILE
   python tools/bench_chains.py --alpha --baseline FILE
@@ -310,6 +318,84 @@ def bench_summary(me, name, X, y, cus, args):
             "burn": burn, "reps": args.reps, "compute_units": cus, "maxlag": lag,
             "method": "tri" if me.tri else "stable", "chains": rows,
             "kernels": {kname: {"code_sha": _kernel_code.code_sha(kname)}}}
+
+
+QUANTILE_PROBS = [0.025, 0.5, 0.975]
+
+
+def hist_kernel_seconds(me, X, y, K, cap, nsamp, maxlag):
+    """Seconds k_trace_hist takes for nsamp samples of K chains: a full ring of `cap` slots
+    added with the quantile sketch enabled less the same add without it (both kernels run on
+    the batch's stream, one behind the other), scaled to nsamp.  Returns (hist, both)."""
+    n, p = X.shape
+    b = me.bb.ChainBatch(me.config(n, p, cap), K, X, y)
+    try:
+        b.init_state()
+        b.run(1, cap - 1, 1, 1, 1)
+        took = []
+        for sketch in (False, True):
+            b.summary_reset(cap, maxlag)
+            if sketch:
+                b.quantiles_reset()
+            b.summary_add(0, 1, 0)  # the first launches are not timed
+            b.sync()
+            t0 = time.perf_counter()
+            b.summary_add(1, cap - 1, 1)
+            b.sync()
+            took.append((time.perf_counter() - t0) * nsamp / (cap - 1))
+        return took[1] - took[0], took[1]
+    finally:
+        b.close()
+
+
+def bench_summary_quantiles(me, name, X, y, cus, args):
+    """The summary call with probs against the summary call without and the trace call,
+    alternated within each round."""
+    bb = me.bb
+    Ks = [k for k in (args.chains or [cus, 4 * cus]) if k <= args.max_chains]
+    nsamp, burn = args.nsamp, args.burn
+    bb.set_seed(SEED)
+    me.summary(y, X, nsamp=200, nchains=2, burn=100, probs=QUANTILE_PROBS)  # warm-up
+    me.summary(y, X, nsamp=200, nchains=2, burn=100)
+    me.chains(y, X, nsamp=200, nchains=2, burn=100)
+    keys = ("quantiles", "summary", "trace", "hist_s", "both_s")
+    v = {K: {k: [] for k in keys} for K in Ks}
+    cap, lag = {}, 0
+    for _ in range(args.reps):
+        for K in Ks:
+            bb.set_seed(SEED)
+            out = me.summary(y, X, nsamp=nsamp, nchains=K, burn=burn, probs=QUANTILE_PROBS)
+            v[K]["quantiles"].append(K * nsamp / out["runtime"])
+            cap[K], lag = bb.last_call_info()["trace_capacity"], out["maxlag"]
+            bb.set_seed(SEED)
+            out = me.summary(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            v[K]["summary"].append(K * nsamp / out["runtime"])
+            bb.set_seed(SEED)
+            out = me.chains(y, X, nsamp=nsamp, nchains=K, burn=burn)
+            v[K]["trace"].append(K * nsamp / out["runtime"])
+            del out
+            h, both = hist_kernel_seconds(me, X, y, K, cap[K], nsamp, lag)
+            v[K]["hist_s"].append(h)
+            v[K]["both_s"].append(both)
+    rows = []
+    for K in Ks:
+        q, s, t = (spread(v[K][k]) for k in ("quantiles", "summary", "trace"))
+        hs = spread(v[K]["hist_s"])
+        rows.append({"chains": K, "ring_capacity": cap[K],
+                     "quantiles_call_sweeps_per_s": q, "summary_call_sweeps_per_s": s,
+                     "trace_call_sweeps_per_s": t,
+                     "quantiles_vs_trace": q["median"] / t["median"],
+                     "quantiles_vs_summary": q["median"] / s["median"],
+                     "k_trace_hist_s": hs, "summary_and_hist_s": spread(v[K]["both_s"]),
+                     "k_trace_hist_share": hs["median"] / (K * nsamp / q["median"])})
+    from bayesbridge_amd import _kernel_code
+
+    return {"design": name, "n": int(X.shape[0]), "p": int(X.shape[1]), "nsamp": nsamp,
+            "burn": burn, "reps": args.reps, "compute_units": cus, "maxlag": lag,
+            "probs": QUANTILE_PROBS, "method": "tri" if me.tri else "stable", "chains": rows,
+            "kernels": {k: {"code_sha": _kernel_code.code_sha(k)}
+                        for k in ("bb::k_trace_hist", "bb::k_quantile_select",
+                                  "bb::k_trace_summary")}}
 
 
 WIDE_BLOCK = 16  # sweeps per launch of the wide kernels' drivers (bb_kernels.h kWideBlock)
@@ -635,6 +721,9 @@ def main():
                     default=[512, 256, 128], help="triangle batch instances to compare (threads)")
     ap.add_argument("--summary", action="store_true",
                     help="the summary mode against the trace call (profiles/chains_summary_*)")
+    ap.add_argument("--quantiles", action="store_true",
+                    help="with --summary: the call with pooled quantiles against the call "
+                         "without and the trace call (profiles/chains_summary_quantiles_*)")
     ap.add_argument("--wide", action="store_true",
                     help="the wide fused chains (key 25) at dbi / bhi (profiles/chains_wide_*)")
     ap.add_argument("--alpha", action="store_true",
@@ -727,6 +816,21 @@ def main():
                       f"[{a['min']:.0f}, {a['max']:.0f}]  kernel {k['median']:.0f}  "
                       f"x{r['vs_sequential_general_path']:.1f} sequential  resident/CU "
                       f"{r['resident_per_cu']}", flush=True)
+            continue
+        if args.summary and args.quantiles:
+            rec = bench_summary_quantiles(me, name, X, y, cus, args)
+            rec["source_sha"] = bb._build.source_sha()
+            stem = "chains_summary_quantiles_tri_" if me.tri else "chains_summary_quantiles_"
+            with open(os.path.join(args.out_dir, f"{stem}{name}{args.tag}.json"), "w") as f:
+                json.dump(rec, f, indent=1)
+                f.write("\n")
+            for r in rec["chains"]:
+                q, s, t = (r[k + "_call_sweeps_per_s"] for k in ("quantiles", "summary", "trace"))
+                print(f"{name} K={r['chains']:5d} quantiles {q['median']:.0f} sweeps/s "
+                      f"[{q['min']:.0f}, {q['max']:.0f}]  summary {s['median']:.0f} "
+                      f"[{s['min']:.0f}, {s['max']:.0f}]  trace {t['median']:.0f} "
+                      f"[{t['min']:.0f}, {t['max']:.0f}]  x{r['quantiles_vs_trace']:.2f} trace  "
+                      f"k_trace_hist {100 * r['k_trace_hist_share']:.2f} %", flush=True)
             continue
         if args.summary:
             rec = bench_summary(me, name, X, y, cus, args)

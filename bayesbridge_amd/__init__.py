@@ -81,7 +81,7 @@ EXPORTED_SYMBOLS = [
     "bridge_reg_logit_chains_summary", "bb_chains_get_omega", "bb_set_em_scratch_budget",
     "bridge_reg_stable_chains_summary_q", "bridge_regression_chains_summary_q",
     "bridge_reg_logit_chains_summary_q", "bb_chains_quantiles_reset", "bb_chains_quantiles_get",
-    "bb_trace_quantiles", "bb_quantile_bin",
+    "bb_trace_quantiles", "bb_quantile_bin", "bb_chain_kernel",
 ]
 
 
@@ -173,6 +173,7 @@ def library(build: bool = True) -> ctypes.CDLL:
     L.bridge_reg_stable_chains.argtypes = [_dp] * 7 + [_dp] * 9 + [_ip] * 4 + [_dp, _ip, _ip]
     L.bb_chains_create.argtypes = [c.POINTER(bb_config), c.c_int, _dp, _dp,
                                    c.POINTER(c.c_void_p)]
+    L.bb_chain_kernel.argtypes = [c.POINTER(bb_config), c.c_int]
     L.bb_chains_destroy.argtypes = [c.c_void_p]
     L.bb_chains_count.argtypes = [c.c_void_p]
     L.bb_chains_resident_per_cu.argtypes = [c.c_void_p]
@@ -1424,6 +1425,16 @@ class EngineConfig:
         if c.p_local <= 0:
             c.p_local = c.p
         return c
+
+
+CHAIN_KERNELS = ("none", "small", "wide", "triangle", "logistic")
+
+
+def chain_kernel(cfg: EngineConfig, batch: bool = False) -> int:
+    """The fused chain kernel family (index into CHAIN_KERNELS) that an Engine (batch False) or
+    a ChainBatch created now from cfg runs; 0: the general path, or for a batch a refusal,
+    whose text library().bb_last_error() then holds.  Needs no device."""
+    return int(library().bb_chain_kernel(ctypes.byref(cfg.to_c()), int(bool(batch))))
 
 
 class Engine:

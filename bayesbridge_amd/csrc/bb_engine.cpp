@@ -156,6 +156,140 @@ static const char *kPhaseNames[PH_COUNT] = {"pre", "scalars", "lambda", "pg", "o
 // the logistic (Polya-Gamma) bridge.
 enum Method { AUTO = 0, CHOL = 1, WOODBURY = 2, ORTHO = 3, TRI = 4, SPARSE = 5, LOGIT = 6 };
 
+// The fused chain path, decided in one place: chain_plan says which kernel
+// family runs a configuration, ChainPath carries that choice and dispatches on it, ChainView is
+// the host's one view of a chain's state and rings.  bb_chain_kernel exports the kinds.
+enum ChainKernel { CK_NONE = 0, CK_SMALL = 1, CK_WIDE = 2, CK_TRI = 3, CK_LOGIT = 4 };
+// mh: the family's alpha-sampling instances run; refusal: why not (CK_NONE), for the batch
+struct ChainPlan { ChainKernel kind; bool mh; const char *refusal; };
+
+// Which fused kernel family runs `c` as a single engine (batch false) or as a chain batch, under
+// the switches of bb_set_tuning keys 25, 26 and 27 (by default their current values).  No device
+// is needed.  Where the batch's rule differs from the engine's, the condition reads `batch` and
+// says so.  The refusals keep the order the batch reports them in.
+ChainPlan chain_plan(const bb_config &c, bool batch, int wide_on = g_chains_wide,
+                     int mh_on = g_fused_alpha, int tri_mh_on = g_fused_tri_alpha) {
+    const bool know_alpha = c.true_alpha > 0;
+    auto no = [](const char *why) { return ChainPlan{CK_NONE, false, why}; };
+    if (c.n <= 0 || c.p <= 0) return no("n and p must be positive");
+    if (c.world > 1) return no("a chain batch runs on one device (world == 1)");
+    // batch only: an engine with world == 1 never looked at p_local
+    if (batch && c.p_local > 0 && c.p_local != c.p)
+        return no("a chain batch holds every column (p_local == p)");
+    if (c.method == TRI) {  // bb_tri.hip; key 27: bb_tri_mh.hip's instances sample alpha
+        static_assert(kTriChainMaxP == 32, "the message below says 32");
+        if (c.p > kTriChainMaxP) return no("a triangle chain batch needs p <= 32");
+        if (c.p > c.n) return no("a triangle chain batch needs p <= n");  // no such engine exists
+        if (!know_alpha && !tri_mh_on)
+            return no("a chain batch needs alpha known (true_alpha > 0)");
+        return {CK_TRI, !know_alpha, nullptr};
+    }
+    if (c.method == LOGIT) {  // bb_logit_chain.hip, alpha known or sampled
+        // batch only: the kernel has no single-chain twin, an engine keeps the general path
+        if (!batch) return no("a logistic engine runs the general path");
+        static_assert(kSmallChainMaxP == 32 && kLogitChainMaxN == 4096, "the messages say so");
+        if (c.p > kSmallChainMaxP) return no("a logistic chain batch needs p <= 32");
+        if (c.p > c.n) return no("a logistic chain batch needs p <= n");
+        if (c.n > kLogitChainMaxN) return no("a logistic chain batch needs n <= 4096");
+        return {CK_LOGIT, !know_alpha, nullptr};
+    }
+    // batch only: with ortho set an engine runs the orthogonal draw, fused, under every other
+    // method value too (2, 3, 5); the batch takes methods 0 and 1 alone
+    if (c.method != AUTO && c.method != CHOL && (batch || !c.ortho))
+        return no("a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or "
+                  "1), the triangle mixture (method 4) or the logistic bridge (method 6)");
+    if (wide_on) {  // key 25: bb_wide.hip's kernel above 32
+        static_assert(kWideChainMaxP == 128, "the message below says 128");
+        if (c.p > kWideChainMaxP) return no("a chain batch needs p <= 128 (wide fused chains on)");
+    } else if (c.p > kSmallChainMaxP) {
+        return no("a chain batch needs p <= 32");
+    }
+    if (c.p > c.n && !c.ortho) return no("a chain batch needs p <= n (or the orthogonal design)");
+    // key 26: bb_small_mh.hip's instances sample alpha, at p <= 32 alone
+    if (!know_alpha && !(mh_on && c.p <= kSmallChainMaxP))
+        return no("a chain batch needs alpha known (true_alpha > 0)");
+    return {c.p <= kSmallChainMaxP ? CK_SMALL : CK_WIDE, !know_alpha, nullptr};
+}
+
+// A chain's state and trace rings as the kernels take them, with the host's widths: p
+// coefficients, `cap` ring slots, the logistic omega's n rows.  at(c): chain c of a batch.
+struct ChainView {
+    ChainState st{};
+    ChainTraces tr{};
+    int p = 0, cap = 1, n = 0;
+    double *omega = nullptr;
+
+    ChainView at(int c) const {
+        ChainView v = *this;
+        auto skip = [](std::initializer_list<double **> qs, size_t k) {
+            for (double **q : qs)
+                if (*q) *q += k;  // an array the family does not have stays null
+        };
+        skip({&v.st.beta, &v.st.lam, &v.st.u, &v.st.shape}, (size_t)c * p);
+        skip({&v.tr.beta, &v.tr.lam, &v.tr.u, &v.tr.shape}, (size_t)c * cap * p);
+        skip({&v.tr.sig2, &v.tr.tau, &v.tr.alpha}, (size_t)c * cap);
+        skip({&v.omega}, (size_t)c * n);
+        v.st.sc += c;
+        v.st.err += c;
+        return v;
+    }
+    SummaryRing ring() const {
+        return {.beta = tr.beta, .sig2 = tr.sig2, .tau = tr.tau, .alpha = tr.alpha, .p = p,
+                .cap = cap};
+    }
+};
+
+// The plan's kind as an engine or a batch stores it (a batch: with its instance), and every
+// choice that follows from it.  A new family adds its case to each switch.
+struct ChainPath {
+    ChainKernel kind = CK_NONE;
+    int packed = 0;     // small batches: the 256-thread instance (key 21 and K >= 2 CUs)
+    int threads = 512;  // triangle batches: the instance, by its threads per workgroup
+
+    // `count` sweeps of the K chains of a batch, or (K == 0) of an engine's own chain
+    void launch(hipStream_t s, int K, const ChainDesign &d, const ChainView &v,
+                const ChainRun &r) const {
+        const char *none = nullptr;  // the family has no instance for this shape
+        if (kind == CK_SMALL) {
+            K ? launch_small_chains(s, K, packed, d, v.st, v.tr, r)
+              : launch_small_chain(s, d, v.st, v.tr, r);
+        } else if (kind == CK_WIDE) {
+            if ((K ? launch_wide_chains(s, K, d, v.st, v.tr, r)
+                   : launch_wide_chain(s, d, v.st, v.tr, r)) != 0)
+                none = K ? "no wide chain-batch instance for this p"
+                         : "no wide fused chain instance for this p";
+        } else if (kind == CK_TRI) {
+            if (K == 0) launch_tri_chain(s, d, v.st, v.tr, r);
+            else if (launch_tri_chains(s, K, threads, d, v.st, v.tr, r) != 0)
+                none = "no triangle chain-batch instance of that many threads";
+        } else if (kind == CK_LOGIT && K) {
+            if (launch_logit_chains(s, K, d, v.st, v.tr, r, v.omega) != 0)
+                none = "no logistic chain-batch instance for this design";
+        } else {
+            none = "no fused chain kernel on this path";
+        }
+        if (none) throw HipError(none);
+    }
+    // workgroups of the batch's instance resident on one CU (-1: the query failed)
+    int resident_per_cu(int n, int p, int mh) const {
+        return kind == CK_TRI     ? tri_chains_resident_per_cu(n, p, threads, mh)
+               : kind == CK_LOGIT ? logit_chains_resident_per_cu(n, p, mh)
+               : kind == CK_WIDE  ? wide_chains_resident_per_cu(p)
+                                  : small_chains_resident_per_cu(n, p, packed, mh);
+    }
+    // threads per workgroup of the batch's instance
+    int block_threads(int p) const {
+        if (kind == CK_WIDE) return wide_chains_threads(p);
+        return kind == CK_TRI ? threads : packed ? 256 : 512;
+    }
+    // Sweeps per launch, and per interrupt poll, of a .C call.  BridgeWrapper.cpp:273-275,
+    // 295-297 poll every 10 sweeps.  A fused launch runs a whole block at ~15-30 us per sweep,
+    // so it polls every 50 (< 2 ms) and pays the launch and LDS-staging prologue once per 50
+    // sweeps instead of per 10.  The wide kernel's sweeps are ~100 us: kWideBlock of them keep
+    // the poll near the general path's 10 sweeps in time.
+    int block() const { return kind == CK_NONE ? 10 : kind == CK_WIDE ? kWideBlock : 50; }
+};
+
 struct bb_engine {
     bb_config cfg{};
     int n = 0, p = 0, p_loc = 0, n_pad = 0, p_pad = 0;
@@ -164,8 +298,7 @@ struct bb_engine {
     int chol_m = 0;
     Method method = AUTO;
     int group = 1;
-    bool fused = false;  // small p: whole sweeps in one launch (bb_small.hip)
-    bool wide = false;   // ... by bb_wide.hip's kernel (32 < p <= 128, key 25 set at creation)
+    ChainPath path;  // whole sweeps in one launch: chain_plan's kernel family at creation
     SparseDesign spd;  // method 5: CSC/CSR design and the Gram pair list
     Hyper hy{};
     hipStream_t stream = nullptr;
@@ -923,6 +1056,22 @@ struct bb_engine {
                 .gdiag = gdiag, .tVc = tVc, .tVr = tVr, .a = tri_a, .d = tri_d, .Gf = tri_G,
                 .ortho = tri() ? cfg.ortho : ortho(), .betaburn = cfg.betaburn, .hy = hy};
     }
+    // this engine's own chain: the general path's fields (the triangle mixture's shape is D)
+    ChainView view() const {
+        return {.st = {.beta = beta, .lam = lam, .u = u, .shape = D, .sc = sc, .err = err},
+                .tr = {.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
+                       .alpha = tr_alpha, .u = tr_u, .shape = tr_shape},
+                .p = p_loc, .cap = cap, .n = n, .omega = omega};
+    }
+    // the C ABI's accessors: f(the view) once `refusal` is null and the stream has drained
+    template <class F>
+    int with_view(const char *refusal, F f) {
+        return guarded([&] {
+            if (refusal) throw HipError(refusal);
+            HIPCHECK(hipStreamSynchronize(stream));
+            f(view());
+        });
+    }
     ChainRun chain_run(uint64_t k1, uint64_t t0, int count, int first_slot, int slot_step,
                        int ring_cap, int mcmc_phase) const {
         return {.k0 = cfg.seed, .k1 = k1, .t0 = t0, .count = count, .first_slot = first_slot,
@@ -932,22 +1081,13 @@ struct bb_engine {
 
     // `count` sweeps from t0 into slots first_slot + k slot_step (mod cap)
     void run(uint64_t t0, int count, int first_slot, int slot_step, int mcmc_phase) {
-        if (fused) {
+        if (path.kind != CK_NONE) {
             if (timing) {
                 sweep_marks.emplace_back();
                 mark(PH_BETA);
             }
-            const ChainState st{.beta = beta, .lam = lam, .u = u, .shape = D, .sc = sc, .err = err};
-            const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
-                                 .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
-            const ChainRun r =
-                chain_run(cfg.stream, t0, count, first_slot, slot_step, cap, mcmc_phase);
-            if (tri())
-                launch_tri_chain(stream, chain_design(), st, tr, r);
-            else if (!wide)
-                launch_small_chain(stream, chain_design(), st, tr, r);
-            else if (launch_wide_chain(stream, chain_design(), st, tr, r) != 0)
-                throw HipError("no wide fused chain instance for this p");
+            path.launch(stream, 0, chain_design(), view(),
+                        chain_run(cfg.stream, t0, count, first_slot, slot_step, cap, mcmc_phase));
             if (timing) mark(PH_END);
             xb_stale = true;  // X beta partials refreshed only if a general sweep needs them
             return;
@@ -1569,23 +1709,14 @@ void engine_setup(bb_engine *e, const double *Xh, const double *yh, const Sparse
         }
     }
     if (e->tri()) tri_setup(e, Xh);
-    // small p, one device, alpha known (or, where key 26 asks for it, sampled in the kernel):
-    // whole sweeps in one single-workgroup launch; the engine keeps the path it was created with
-    e->fused = (e->method == CHOL || e->ortho()) && c.p <= kSmallChainMaxP && c.world == 1 &&
-               (e->hy.know_alpha || g_fused_alpha) && e->cvec && e->gdiag &&
-               (e->ortho() || e->G);
-    // the same for 32 < p <= 128 where key 25 asks for it (bb_wide.hip); the engine keeps the
-    // kernel it was created with
-    e->wide = g_chains_wide && (e->method == CHOL || e->ortho()) && c.p > kSmallChainMaxP &&
-              c.p <= kWideChainMaxP && (c.p <= c.n || e->ortho()) && c.world == 1 &&
-              e->hy.know_alpha && e->cvec && e->gdiag && (e->ortho() || e->G);
-    if (e->wide) e->fused = true;
-    // bb_tri.hip k_tri_chain (general and orthogonal designs); alpha sampled in the kernel where
-    // key 27 asks for it (bb_tri_mh.hip, p <= n as its batch)
-    if (e->tri())
-        e->fused = c.p <= kTriChainMaxP && c.world == 1 &&
-                   (e->hy.know_alpha || (g_fused_tri_alpha && c.p <= c.n)) &&
-                   (!c.ortho || (e->tri_G && e->cvec));
+    // whole sweeps in one single-workgroup launch where the plan says so (a CSC design never);
+    // the engine keeps the path it was created with.  What the kernels read follows from the
+    // same configuration above: a plan without its buffers is an error, not the general path.
+    if (!spin) e->path.kind = chain_plan(c, false).kind;
+    if (e->path.kind != CK_NONE &&
+        !(e->tri() ? e->tVc && (!c.ortho || (e->tri_G && e->cvec))
+                   : e->cvec && e->gdiag && (e->ortho() || e->G)))
+        throw HipError("the fused chain's design buffers are missing");
     if (e->nid) nid_certify_lambda(e);
     HIPCHECK(hipStreamSynchronize(e->stream));
 }
@@ -1752,42 +1883,70 @@ struct Throttle {
     }
 };
 
-// Why a configuration cannot run as a chain batch (nullptr: it can): the batch kernel is the
-// fused small chain, so the conditions are those of bb_engine::fused for the stable mixture.
-const char *chains_refusal(const bb_config &c) {
-    if (c.n <= 0 || c.p <= 0) return "n and p must be positive";
-    if (c.world > 1) return "a chain batch runs on one device (world == 1)";
-    if (c.p_local > 0 && c.p_local != c.p) return "a chain batch holds every column (p_local == p)";
-    if (c.method == TRI) {  // the triangle mixture: where bb_engine::fused runs k_tri_chain
-        static_assert(kTriChainMaxP == 32, "the message below says 32");
-        if (c.p > kTriChainMaxP) return "a triangle chain batch needs p <= 32";
-        if (c.p > c.n) return "a triangle chain batch needs p <= n";
-        // bb_set_tuning key 27: bb_tri_mh.hip's instances sample alpha
-        if (!(c.true_alpha > 0) && !g_fused_tri_alpha)
-            return "a chain batch needs alpha known (true_alpha > 0)";
-        return nullptr;
-    }
-    if (c.method == LOGIT) {  // the logistic bridge: bb_logit_chain.hip, alpha known or sampled
-        static_assert(kSmallChainMaxP == 32 && kLogitChainMaxN == 4096, "the messages say so");
-        if (c.p > kSmallChainMaxP) return "a logistic chain batch needs p <= 32";
-        if (c.p > c.n) return "a logistic chain batch needs p <= n";
-        if (c.n > kLogitChainMaxN) return "a logistic chain batch needs n <= 4096";
-        return nullptr;
-    }
-    if (c.method != AUTO && c.method != CHOL)
-        return "a chain batch runs the stable mixture's Cholesky or orthogonal draw (method 0 or "
-               "1), the triangle mixture (method 4) or the logistic bridge (method 6)";
-    if (g_chains_wide) {  // bb_set_tuning key 25: bb_wide.hip's kernel above 32
-        static_assert(kWideChainMaxP == 128, "the message below says 128");
-        if (c.p > kWideChainMaxP) return "a chain batch needs p <= 128 (wide fused chains on)";
-    } else if (c.p > kSmallChainMaxP) {
-        return "a chain batch needs p <= 32";
-    }
-    if (c.p > c.n && !c.ortho) return "a chain batch needs p <= n (or the orthogonal design)";
-    // bb_set_tuning key 26: bb_small_mh.hip's instances sample alpha, at p <= 32 alone
-    if (!(c.true_alpha > 0) && !(g_fused_alpha && c.p <= kSmallChainMaxP))
-        return "a chain batch needs alpha known (true_alpha > 0)";
-    return nullptr;
+// The C ABI's accessors over one chain's view, an engine's or chain c's of a batch: each makes
+// the f(view) that bb_engine::with_view or bb_chains::with_chain runs once the stream has
+// drained.  Trace ring slots (a null output is skipped), the current state, the triangle
+// mixture's u, the logistic omega.
+auto chain_get_trace(int slot0, int count, const Traces &o) {
+    return [=](const ChainView &v) {
+        const size_t pl = (size_t)v.p;
+        ring_fetch(slot0, count, v.cap,
+                   {{o.beta, v.tr.beta, pl}, {o.lam, v.tr.lam, pl}, {o.sig2, v.tr.sig2, 1},
+                    {o.tau, v.tr.tau, 1}, {o.alpha, v.tr.alpha, 1}, {o.u, v.tr.u, pl},
+                    {o.shape, v.tr.shape, pl}});
+    };
+}
+auto chain_get_state(double *beta, double *lambda, double *tau, double *sig2, double *alpha) {
+    return [=](const ChainView &v) {
+        const size_t pb = (size_t)v.p * sizeof(double);
+        if (beta) HIPCHECK(hipMemcpy(beta, v.st.beta, pb, hipMemcpyDeviceToHost));
+        if (lambda) HIPCHECK(hipMemcpy(lambda, v.st.lam, pb, hipMemcpyDeviceToHost));
+        scalars_read(v.st.sc, tau, sig2, alpha);
+    };
+}
+auto chain_set_state(const double *beta, double tau, double sig2, double alpha) {
+    return [=](const ChainView &v) {
+        HIPCHECK(hipMemcpy(v.st.beta, beta, (size_t)v.p * sizeof(double), hipMemcpyHostToDevice));
+        scalars_write(v.st.sc, tau, sig2, alpha);
+    };
+}
+auto chain_set_tri_state(const double *u) {
+    return [=](const ChainView &v) {
+        HIPCHECK(hipMemcpy(v.st.u, u, (size_t)v.p * sizeof(double), hipMemcpyHostToDevice));
+    };
+}
+auto chain_get_omega(double *omega) {
+    return [=](const ChainView &v) {
+        HIPCHECK(hipMemcpy(omega, v.omega, (size_t)v.n * sizeof(double), hipMemcpyDeviceToHost));
+    };
+}
+
+// Trace slots [slot0, slot0 + count) of EVERY one of the K chains of `v` -> samples [s0, s0 +
+// count) of the P x M x K (M x K) outputs: one strided copy per contiguous run of ring and trace.
+void chain_copy_out(const ChainView &v, int K, int slot0, int count, int s0, int m,
+                    const Traces &o) {
+    const int cap = v.cap;
+    auto strided = [&](double *dst, const double *src, size_t w, int k, int sl, int run) {
+        if (!dst) return;
+        if (K == 1 || (run == cap && run == m)) {  // one contiguous block (no ring wrap)
+            ring_copy(dst + (size_t)(s0 + k) * w, src + (size_t)sl * w, (size_t)K * run * w);
+            return;
+        }
+        HIPCHECK(hipMemcpy2D(dst + (size_t)(s0 + k) * w, (size_t)m * w * sizeof(double),
+                             src + (size_t)sl * w, (size_t)cap * w * sizeof(double),
+                             (size_t)run * w * sizeof(double), (size_t)K,
+                             hipMemcpyDeviceToHost));
+    };
+    const size_t p = (size_t)v.p;
+    ring_runs(slot0, count, cap, [&](int k, int sl, int run) {
+        strided(o.beta, v.tr.beta, p, k, sl, run);
+        strided(o.lam, v.tr.lam, p, k, sl, run);
+        strided(o.sig2, v.tr.sig2, 1, k, sl, run);
+        strided(o.tau, v.tr.tau, 1, k, sl, run);
+        strided(o.alpha, v.tr.alpha, 1, k, sl, run);
+        strided(o.u, v.tr.u, p, k, sl, run);
+        strided(o.shape, v.tr.shape, p, k, sl, run);
+    });
 }
 
 }  // namespace
@@ -1799,135 +1958,91 @@ const char *chains_refusal(const bb_config &c) {
 // One engine (`proto`, never run) holds what the chains share -- X, y, X'X, X'y, the
 // triangle mixture's SVD basis and the least-squares start -- and makes each chain's pre-burn
 // draw under that chain's key; the state, the error word and the trace rings are per chain
-// ([chain][p], [chain][slot][p]).
+// ([chain][p], [chain][slot][p]): `v` views them all, v.at(c) chain c's.
 // ---------------------------------------------------------------------------
 struct bb_chains {
     bb_engine *proto = nullptr;
-    int K = 0, p = 0, cap = 1;
+    int K = 0;
     std::vector<void *> owned;
-    double *beta = nullptr, *lam = nullptr;
-    DevScalars *sc = nullptr, *sc0 = nullptr;  // sc0: the scalars every chain starts from
-    uint32_t *err = nullptr;
-    double *tr_beta = nullptr, *tr_lam = nullptr, *tr_sig2 = nullptr, *tr_tau = nullptr,
-           *tr_alpha = nullptr;
-    // triangle mixture (proto->tri()): u and shape beside omega (lam)
-    double *u = nullptr, *shape = nullptr, *tr_u = nullptr, *tr_shape = nullptr;
-    double *omega = nullptr;  // logistic bridge: [chain][n], the omega of the last sweep
+    ChainView v;  // u and shape: the triangle mixture's alone; omega ([chain][n]): the logistic
+    DevScalars *sc0 = nullptr;  // the scalars every chain starts from
     Throttle ahead;
+    uint64_t base_stream = 0;
+    ChainPath path;  // chain_plan's family at creation, with the batch's instance
 
-    bool tri() const { return proto->tri(); }
-    bool logit() const { return proto->logit(); }
+    bool tri() const { return path.kind == CK_TRI; }
+    bool logit() const { return path.kind == CK_LOGIT; }
     ~bb_chains() {
         if (proto && proto->stream) (void)hipStreamSynchronize(proto->stream);
         for (void *q : owned) (void)hipFree(q);
         delete proto;
     }
     hipStream_t stream() const { return proto->stream; }
-    void check_chain(int c) const {
+    ChainView chain(int c) const {
         if (c < 0 || c >= K) throw HipError("chain index out of range");
+        return v.at(c);
+    }
+    // f(chain c's view) once c is in range, `refusal` is null and the stream has drained
+    template <class F>
+    int with_chain(int c, const char *refusal, F f) {
+        return guarded([&] {
+            const ChainView vc = chain(c);
+            if (refusal) throw HipError(refusal);
+            HIPCHECK(hipStreamSynchronize(stream()));
+            f(vc);
+        });
     }
 
     void init_state() {
         bb_engine *e = proto;
         hipStream_t s = e->stream;
-        const size_t pb = (size_t)p * sizeof(double);
+        const size_t pb = (size_t)v.p * sizeof(double);
+        auto d2d = [&](void *dst, const void *src, size_t bytes) {
+            HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+        };
         e->cfg.stream = base_stream;
         engine_init_state_local(e);  // least-squares start, starting scalars, X beta
-        HIPCHECK(hipMemcpyAsync(sc0, e->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
-        if (!tri()) HIPCHECK(hipMemsetAsync(lam, 0, (size_t)K * pb, s));
+        d2d(sc0, e->sc, sizeof(DevScalars));
+        if (!tri()) HIPCHECK(hipMemsetAsync(v.st.lam, 0, (size_t)K * pb, s));
         for (int c = 0; c < K; ++c) {
-            const size_t ring = (size_t)c * cap;
+            const ChainView vc = v.at(c);
             // the pre-burn draw under the chain's own key, from the shared starting scalars
-            HIPCHECK(hipMemcpyAsync(e->sc, sc0, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
+            d2d(e->sc, sc0, sizeof(DevScalars));
             e->clear_err();
             e->cfg.stream = base_stream + (uint64_t)c;
             engine_preburn_draw(e);
             if (tri()) {  // u = 0.5, omega = 1 and their trace slot 0, as engine_init_state_local
-                HIPCHECK(hipMemcpyAsync(u + (size_t)c * p, e->u, pb, hipMemcpyDeviceToDevice, s));
-                HIPCHECK(hipMemcpyAsync(lam + (size_t)c * p, e->lam, pb, hipMemcpyDeviceToDevice, s));
-                HIPCHECK(hipMemcpyAsync(tr_u + ring * p, e->tr_u, pb, hipMemcpyDeviceToDevice, s));
-                HIPCHECK(hipMemcpyAsync(tr_lam + ring * p, e->tr_lam, pb, hipMemcpyDeviceToDevice, s));
+                d2d(vc.st.u, e->u, pb);
+                d2d(vc.st.lam, e->lam, pb);
+                d2d(vc.tr.u, e->tr_u, pb);
+                d2d(vc.tr.lam, e->tr_lam, pb);
             }
-            HIPCHECK(hipMemcpyAsync(beta + (size_t)c * p, e->beta, pb, hipMemcpyDeviceToDevice, s));
-            HIPCHECK(hipMemcpyAsync(sc + c, e->sc, sizeof(DevScalars), hipMemcpyDeviceToDevice, s));
-            HIPCHECK(hipMemcpyAsync(err + c, e->err, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            d2d(vc.st.beta, e->beta, pb);
+            d2d(vc.st.sc, e->sc, sizeof(DevScalars));
+            d2d(vc.st.err, e->err, sizeof(uint32_t));
             // trace slot 0: the starting values, as a single engine leaves them
-            HIPCHECK(hipMemcpyAsync(tr_beta + ring * p, e->beta, pb, hipMemcpyDeviceToDevice, s));
-            HIPCHECK(hipMemcpyAsync(tr_tau + ring, e->tr_tau, sizeof(double),
-                                    hipMemcpyDeviceToDevice, s));
-            HIPCHECK(hipMemcpyAsync(tr_sig2 + ring, e->tr_sig2, sizeof(double),
-                                    hipMemcpyDeviceToDevice, s));
-            HIPCHECK(hipMemcpyAsync(tr_alpha + ring, e->tr_alpha, sizeof(double),
-                                    hipMemcpyDeviceToDevice, s));
+            d2d(vc.tr.beta, e->beta, pb);
+            d2d(vc.tr.tau, e->tr_tau, sizeof(double));
+            d2d(vc.tr.sig2, e->tr_sig2, sizeof(double));
+            d2d(vc.tr.alpha, e->tr_alpha, sizeof(double));
         }
         e->cfg.stream = base_stream;
         e->clear_err();
         HIPCHECK(hipStreamSynchronize(s));
     }
 
-    void run(uint64_t t0, int count, int first_slot, int slot_step, int mcmc_phase) {
-        bb_engine *e = proto;
-        const ChainState st{.beta = beta, .lam = lam, .u = u, .shape = shape, .sc = sc, .err = err};
-        const ChainTraces tr{.beta = tr_beta, .lam = tr_lam, .sig2 = tr_sig2, .tau = tr_tau,
-                             .alpha = tr_alpha, .u = tr_u, .shape = tr_shape};
-        const ChainRun r =
-            e->chain_run(base_stream, t0, count, first_slot, slot_step, cap, mcmc_phase);
-        if (logit()) {
-            if (launch_logit_chains(e->stream, K, e->chain_design(), st, tr, r, omega) != 0)
-                throw HipError("no logistic chain-batch instance for this design");
-        } else if (wide) {
-            if (launch_wide_chains(e->stream, K, e->chain_design(), st, tr, r) != 0)
-                throw HipError("no wide chain-batch instance for this p");
-        } else if (!tri())
-            launch_small_chains(e->stream, K, packed, e->chain_design(), st, tr, r);
-        else if (launch_tri_chains(e->stream, K, threads, e->chain_design(), st, tr, r) != 0)
-            throw HipError("no triangle chain-batch instance of that many threads");
-    }
-
-    void throttle() { ahead.mark(stream()); }
-
-    // Trace slots [slot0, slot0 + count) of EVERY chain -> samples [s0, s0 + count) of the
-    // P x M x K (M x K) outputs: one strided copy per contiguous run of the ring and trace.
-    void copy_out(int slot0, int count, int s0, int m, const Traces &o) {
-        auto strided = [&](double *dst, const double *src, size_t w, int k, int sl, int run) {
-            if (!dst) return;
-            if (K == 1 || (run == cap && run == m)) {  // one contiguous block (no ring wrap)
-                ring_copy(dst + (size_t)(s0 + k) * w, src + (size_t)sl * w,
-                          (size_t)K * run * w);
-                return;
-            }
-            HIPCHECK(hipMemcpy2D(dst + (size_t)(s0 + k) * w, (size_t)m * w * sizeof(double),
-                                 src + (size_t)sl * w, (size_t)cap * w * sizeof(double),
-                                 (size_t)run * w * sizeof(double), (size_t)K,
-                                 hipMemcpyDeviceToHost));
-        };
-        ring_runs(slot0, count, cap, [&](int k, int sl, int run) {
-            strided(o.beta, tr_beta, (size_t)p, k, sl, run);
-            strided(o.lam, tr_lam, (size_t)p, k, sl, run);
-            strided(o.sig2, tr_sig2, 1, k, sl, run);
-            strided(o.tau, tr_tau, 1, k, sl, run);
-            strided(o.alpha, tr_alpha, 1, k, sl, run);
-            strided(o.u, tr_u, (size_t)p, k, sl, run);
-            strided(o.shape, tr_shape, (size_t)p, k, sl, run);
-        });
-    }
-
     // The optional device-side summary of all K chains (bb_summary.hip): created by
     // summary_reset, fed ring slots on the batch's stream behind the sweeps that wrote them.
     std::unique_ptr<TraceSummary> summary;
-    SummaryRing summary_ring() const {
-        return {.beta = tr_beta, .sig2 = tr_sig2, .tau = tr_tau, .alpha = tr_alpha, .p = p,
-                .cap = cap};
-    }
     void summary_reset(int nsamp, int maxlag) {
         if (!summary) summary.reset(new TraceSummary());
         quant.reset();  // a sketch belongs to one summary: quantiles_reset enables it again
-        summary->reset(stream(), K, p + 3, nsamp, maxlag);
+        summary->reset(stream(), K, v.p + 3, nsamp, maxlag);
     }
     void summary_add(int slot0, int count, int s0) {
         if (!summary) throw HipError("summary: add before reset");
-        summary->add(stream(), summary_ring(), slot0, count, s0);
-        if (quant) quant->add(stream(), summary_ring(), K, slot0, count, s0);
+        summary->add(stream(), v.ring(), slot0, count, s0);
+        if (quant) quant->add(stream(), v.ring(), K, slot0, count, s0);
     }
     // The optional pooled quantile sketch (bb_quantile.hip) of the samples the summary takes:
     // enabled after summary_reset and before the first summary_add, fed by summary_add.
@@ -1937,7 +2052,7 @@ struct bb_chains {
         if (summary->next != 0) throw HipError("quantiles: reset before the first summary_add");
         if (!quant) quant.reset(new TraceQuantiles());
         try {
-            quant->reset(stream(), K, p + 3, summary->M);
+            quant->reset(stream(), K, v.p + 3, summary->M);
         } catch (...) {
             quant.reset();
             throw;
@@ -1955,18 +2070,10 @@ struct bb_chains {
         summary->get(stream(), mean, var, acov, hmean, hvar);
         if (flags) {
             static_assert(sizeof(int) == sizeof(uint32_t), "flags are 32-bit words");
-            HIPCHECK(hipMemcpy(flags, err, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIPCHECK(hipMemcpy(flags, v.st.err, (size_t)K * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost));
         }
     }
-
-    uint64_t base_stream = 0;
-    // the 256-thread instance (two chains per CU): bb_set_tuning key 21 and K >= 2 CUs
-    int packed = 0;
-    // the triangle batch's instance, by its threads per workgroup (bb_chains_create)
-    int threads = 512;
-    // bb_wide.hip's k_wide_chains (32 < p <= 128; bb_set_tuning key 25 at creation)
-    bool wide = false;
-    int block() const { return wide ? kWideBlock : 50; }  // sweeps per launch of a .C call
 };
 
 // ---------------------------------------------------------------------------
@@ -2144,36 +2251,18 @@ int bb_engine_sync(bb_engine *e) {
 
 int bb_engine_get_trace(bb_engine *e, int slot0, int count, double *beta, double *lambda,
                         double *sig2, double *tau, double *alpha) {
-    return guarded([&] {
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        const size_t pl = (size_t)e->p_loc;
-        ring_fetch(slot0, count, e->cap,
-                   {{beta, e->tr_beta, pl}, {lambda, e->tr_lam, pl}, {sig2, e->tr_sig2, 1},
-                    {tau, e->tr_tau, 1}, {alpha, e->tr_alpha, 1}});
-    });
+    return e->with_view(nullptr, chain_get_trace(slot0, count, {beta, lambda, sig2, tau, alpha}));
 }
 
 int bb_engine_get_state(bb_engine *e, double *beta, double *lambda, double *tau, double *sig2,
                         double *alpha) {
-    return guarded([&] {
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        if (beta)
-            HIPCHECK(hipMemcpy(beta, e->beta, (size_t)e->p_loc * sizeof(double),
-                               hipMemcpyDeviceToHost));
-        if (lambda)
-            HIPCHECK(hipMemcpy(lambda, e->lam, (size_t)e->p_loc * sizeof(double),
-                               hipMemcpyDeviceToHost));
-        scalars_read(e->sc, tau, sig2, alpha);
-    });
+    return e->with_view(nullptr, chain_get_state(beta, lambda, tau, sig2, alpha));
 }
 
 int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig2,
                         double alpha) {
-    return guarded([&] {
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        HIPCHECK(hipMemcpy(e->beta, beta, (size_t)e->p_loc * sizeof(double),
-                           hipMemcpyHostToDevice));
-        scalars_write(e->sc, tau, sig2, alpha);
+    return e->with_view(nullptr, [&](const ChainView &v) {
+        chain_set_state(beta, tau, sig2, alpha)(v);
         e->xbeta();
         HIPCHECK(hipStreamSynchronize(e->stream));
     });
@@ -2182,28 +2271,17 @@ int bb_engine_set_state(bb_engine *e, const double *beta, double tau, double sig
 int bb_engine_method(const bb_engine *e) { return e->method; }
 
 int bb_engine_get_omega(bb_engine *e, double *omega) {
-    return guarded([&] {
-        if (!e->logit()) throw HipError("not a logistic engine");
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        HIPCHECK(hipMemcpy(omega, e->omega, (size_t)e->n * sizeof(double), hipMemcpyDeviceToHost));
-    });
+    return e->with_view(e->logit() ? nullptr : "not a logistic engine", chain_get_omega(omega));
 }
 
 int bb_engine_get_tri_trace(bb_engine *e, int slot0, int count, double *u, double *shape) {
-    return guarded([&] {
-        if (!e->tri()) throw HipError("not a triangle-method engine");
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        const size_t pl = (size_t)e->p_loc;
-        ring_fetch(slot0, count, e->cap, {{u, e->tr_u, pl}, {shape, e->tr_shape, pl}});
-    });
+    return e->with_view(e->tri() ? nullptr : "not a triangle-method engine",
+                        chain_get_trace(slot0, count, {.u = u, .shape = shape}));
 }
 
 int bb_engine_set_tri_state(bb_engine *e, const double *u) {
-    return guarded([&] {
-        if (!e->tri()) throw HipError("not a triangle-method engine");
-        HIPCHECK(hipStreamSynchronize(e->stream));
-        HIPCHECK(hipMemcpy(e->u, u, (size_t)e->p_loc * sizeof(double), hipMemcpyHostToDevice));
-    });
+    return e->with_view(e->tri() ? nullptr : "not a triangle-method engine",
+                        chain_set_tri_state(u));
 }
 
 int bb_engine_get_tri_basis(bb_engine *e, double *tV, double *a, double *d) {
@@ -2418,6 +2496,13 @@ int bb_engine_error_flags(bb_engine *e, uint32_t *flags) {
 // ---------------------------------------------------------------------------
 // Chain batch (struct bb_chains above)
 // ---------------------------------------------------------------------------
+int bb_chain_kernel(const bb_config *cfg, int batch) {
+    g_last_error.clear();
+    const ChainPlan plan = chain_plan(*cfg, batch != 0);
+    if (batch && plan.refusal) set_error("%s", plan.refusal);
+    return plan.kind;
+}
+
 int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const double *y,
                      bb_chains **out) {
     *out = nullptr;
@@ -2425,57 +2510,48 @@ int bb_chains_create(const bb_config *cfg, int nchains, const double *X, const d
         set_error("bb_chains_create: nchains must be at least 1 (got %d)", nchains);
         return -1;
     }
-    if (const char *why = chains_refusal(*cfg)) {
-        set_error("bb_chains_create: %s", why);
+    const ChainPlan plan = chain_plan(*cfg, true);
+    if (plan.refusal) {
+        set_error("bb_chains_create: %s", plan.refusal);
         return -1;
     }
     bb_chains *b = new bb_chains();
     try {
         bb_config c = *cfg;
         b->K = nchains;
-        b->p = c.p;
-        b->cap = c.trace_capacity < 1 ? 1 : c.trace_capacity;
         b->base_stream = c.stream;
         c.p_local = c.p;
         c.trace_capacity = 1;  // the shared engine records its own slot 0 only
         if (bb_engine_create(&c, X, y, &b->proto) != 0) throw HipError(g_last_error);
-        // (the logistic prototype is a general-path engine: its batch kernel has no single-chain
-        // twin, so there is no bb_engine::fused to ask for)
-        if (b->proto->logit() != (c.method == LOGIT) ||
-            (!b->proto->logit() && (!b->proto->fused || b->proto->tri() != (c.method == TRI))))
+        // the prototype's own plan is the batch's by construction of chain_plan (but for the
+        // logistic bridge, whose kernel has no single-chain twin), so this cannot fire
+        if (plan.kind != CK_LOGIT && b->proto->path.kind != plan.kind)
             throw HipError("this design does not run as a fused small chain");
         int cus = 0;
         HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
-        b->wide = b->proto->wide;
+        b->path.kind = plan.kind;
         // (alpha sampled, key 26: the 512-thread instance at every K, there is no packed one)
-        b->packed = !b->tri() && !b->wide && g_chains_packed && nchains >= 2 * cus &&
-                    b->proto->hy.know_alpha;
+        b->path.packed =
+            plan.kind == CK_SMALL && g_chains_packed && nchains >= 2 * cus && !plan.mh;
         // more triangle chains than the 512-thread instance holds at once (one per CU): a
         // narrower instance, several per CU, the same bits
-        if (b->tri())
-            b->threads = tri_chains_threads(c.n, c.p, nchains, cus, !b->proto->hy.know_alpha);
+        if (b->tri()) b->path.threads = tri_chains_threads(c.n, c.p, nchains, cus, plan.mh);
         auto &o = b->owned;
-        const size_t K = (size_t)nchains, p = (size_t)c.p, cap = (size_t)b->cap;
-        b->beta = dalloc<double>(K * p, o);
-        b->lam = dalloc<double>(K * p, o);
-        b->sc = dalloc<DevScalars>(K, o);
+        ChainView &v = b->v;
+        v.p = c.p;
+        v.cap = cfg->trace_capacity < 1 ? 1 : cfg->trace_capacity;
+        v.n = c.n;
+        const size_t K = (size_t)nchains, p = (size_t)c.p, ring = (size_t)v.cap;
+        // [chain][w] doubles, zeroed; `on` false: the family has no such array
+        auto rows = [&](size_t w, bool on = true) { return on ? dalloc<double>(K * w, o) : nullptr; };
+        v.st = {.beta = rows(p), .lam = rows(p), .u = rows(p, b->tri()),
+                .shape = rows(p, b->tri()), .sc = dalloc<DevScalars>(K, o),
+                .err = dalloc<uint32_t>(K, o)};
+        v.tr = {.beta = rows(ring * p), .lam = rows(ring * p), .sig2 = rows(ring),
+                .tau = rows(ring), .alpha = rows(ring), .u = rows(ring * p, b->tri()),
+                .shape = rows(ring * p, b->tri())};
+        v.omega = rows((size_t)c.n, b->logit());
         b->sc0 = dalloc<DevScalars>(1, o);
-        b->err = dalloc<uint32_t>(K, o);
-        b->tr_beta = dalloc<double>(K * cap * p, o);
-        b->tr_lam = dalloc<double>(K * cap * p, o);
-        b->tr_sig2 = dalloc<double>(K * cap, o);
-        b->tr_tau = dalloc<double>(K * cap, o);
-        b->tr_alpha = dalloc<double>(K * cap, o);
-        if (b->tri()) {
-            b->u = dalloc<double>(K * p, o);
-            b->shape = dalloc<double>(K * p, o);
-            b->tr_u = dalloc<double>(K * cap * p, o);
-            b->tr_shape = dalloc<double>(K * cap * p, o);
-        }
-        if (b->logit()) {
-            b->omega = dalloc<double>(K * (size_t)c.n, o);
-            HIPCHECK(hipMemset(b->omega, 0, K * (size_t)c.n * sizeof(double)));
-        }
     } catch (std::exception &ex) {
         const std::string msg = ex.what();
         delete b;
@@ -2491,27 +2567,18 @@ int bb_chains_count(const bb_chains *b) { return b->K; }
 
 int bb_chains_resident_per_cu(const bb_chains *b) {
     if (hipSetDevice(b->proto->cfg.device) != hipSuccess) return -1;
-    if (b->tri())
-        return tri_chains_resident_per_cu(b->proto->n, b->p, b->threads,
-                                          !b->proto->hy.know_alpha);
-    if (b->logit())
-        return logit_chains_resident_per_cu(b->proto->n, b->p, !b->proto->hy.know_alpha);
-    if (b->wide) return wide_chains_resident_per_cu(b->p);
-    return small_chains_resident_per_cu(b->proto->n, b->p, b->packed, !b->proto->hy.know_alpha);
+    return b->path.resident_per_cu(b->proto->n, b->v.p, !b->proto->hy.know_alpha);
 }
 
-int bb_chains_threads(const bb_chains *b) {
-    if (b->wide) return wide_chains_threads(b->p);
-    return b->tri() ? b->threads : b->packed ? 256 : 512;
-}
+int bb_chains_threads(const bb_chains *b) { return b->path.block_threads(b->v.p); }
 
 int bb_chains_set_threads(bb_chains *b, int threads) {
     if (!b->tri() || hipSetDevice(b->proto->cfg.device) != hipSuccess ||
-        tri_chains_resident_per_cu(b->proto->n, b->p, threads, !b->proto->hy.know_alpha) < 0) {
+        tri_chains_resident_per_cu(b->proto->n, b->v.p, threads, !b->proto->hy.know_alpha) < 0) {
         set_error("bb_chains_set_threads: no triangle chain-batch instance of %d threads", threads);
         return -1;
     }
-    b->threads = threads;
+    b->path.threads = threads;
     return 0;
 }
 
@@ -2523,7 +2590,9 @@ int bb_chains_run(bb_chains *b, uint64_t t0, int count, int first_slot, int slot
                   int mcmc_phase) {
     // mcmc_phase selects the prior of the alpha MH step (batches created under key 26 or 27)
     return guarded(b->proto->cfg.device, [&] {
-        b->run(t0, count, first_slot, slot_step, mcmc_phase);
+        b->path.launch(b->stream(), b->K, b->proto->chain_design(), b->v,
+                       b->proto->chain_run(b->base_stream, t0, count, first_slot, slot_step,
+                                           b->v.cap, mcmc_phase));
         HIPCHECK(hipGetLastError());
     });
 }
@@ -2534,79 +2603,40 @@ int bb_chains_sync(bb_chains *b) {
 
 int bb_chains_get_trace(bb_chains *b, int chain, int slot0, int count, double *beta,
                         double *lambda, double *sig2, double *tau, double *alpha) {
-    return guarded([&] {
-        b->check_chain(chain);
-        if (slot0 < 0 || count < 0) throw HipError("bb_chains_get_trace: slot0 and count must be >= 0");
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-        const size_t pl = (size_t)b->p, ring = (size_t)chain * b->cap;
-        ring_fetch(slot0, count, b->cap,
-                   {{beta, b->tr_beta + ring * pl, pl}, {lambda, b->tr_lam + ring * pl, pl},
-                    {sig2, b->tr_sig2 + ring, 1}, {tau, b->tr_tau + ring, 1},
-                    {alpha, b->tr_alpha + ring, 1}});
-    });
+    return b->with_chain(
+        chain,
+        slot0 < 0 || count < 0 ? "bb_chains_get_trace: slot0 and count must be >= 0" : nullptr,
+        chain_get_trace(slot0, count, {beta, lambda, sig2, tau, alpha}));
 }
 
 int bb_chains_get_state(bb_chains *b, int chain, double *beta, double *lambda, double *tau,
                         double *sig2, double *alpha) {
-    return guarded([&] {
-        b->check_chain(chain);
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-        const size_t pl = (size_t)b->p;
-        if (beta)
-            HIPCHECK(hipMemcpy(beta, b->beta + chain * pl, pl * sizeof(double),
-                               hipMemcpyDeviceToHost));
-        if (lambda)
-            HIPCHECK(hipMemcpy(lambda, b->lam + chain * pl, pl * sizeof(double),
-                               hipMemcpyDeviceToHost));
-        scalars_read(b->sc + chain, tau, sig2, alpha);
-    });
+    return b->with_chain(chain, nullptr, chain_get_state(beta, lambda, tau, sig2, alpha));
 }
 
 int bb_chains_set_state(bb_chains *b, int chain, const double *beta, double tau, double sig2,
                         double alpha) {
-    return guarded([&] {
-        b->check_chain(chain);
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-        const size_t pl = (size_t)b->p;
-        HIPCHECK(hipMemcpy(b->beta + chain * pl, beta, pl * sizeof(double),
-                           hipMemcpyHostToDevice));
-        scalars_write(b->sc + chain, tau, sig2, alpha);
-    });
+    return b->with_chain(chain, nullptr, chain_set_state(beta, tau, sig2, alpha));
 }
 
 int bb_chains_get_omega(bb_chains *b, int chain, double *omega) {
-    return guarded([&] {
-        b->check_chain(chain);
-        if (!b->logit()) throw HipError("not a logistic chain batch");
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-        const size_t n = (size_t)b->proto->n;
-        HIPCHECK(hipMemcpy(omega, b->omega + chain * n, n * sizeof(double),
-                           hipMemcpyDeviceToHost));
-    });
+    return b->with_chain(chain, b->logit() ? nullptr : "not a logistic chain batch",
+                         chain_get_omega(omega));
 }
 
 int bb_chains_get_tri_trace(bb_chains *b, int chain, int slot0, int count, double *u,
                             double *shape) {
-    return guarded([&] {
-        b->check_chain(chain);
-        if (!b->tri()) throw HipError("not a triangle-method chain batch");
-        if (slot0 < 0 || count < 0)
-            throw HipError("bb_chains_get_tri_trace: slot0 and count must be >= 0");
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-        const size_t pl = (size_t)b->p, ring = (size_t)chain * b->cap;
-        ring_fetch(slot0, count, b->cap,
-                   {{u, b->tr_u + ring * pl, pl}, {shape, b->tr_shape + ring * pl, pl}});
-    });
+    return b->with_chain(
+        chain,
+        !b->tri()                 ? "not a triangle-method chain batch"
+        : slot0 < 0 || count < 0 ? "bb_chains_get_tri_trace: slot0 and count must be >= 0"
+                                  : nullptr,
+        chain_get_trace(slot0, count, {.u = u, .shape = shape}));
 }
 
 int bb_chains_set_tri_state(bb_chains *b, int chain, const double *u) {
-    return guarded([&] {
-        b->check_chain(chain);
-        if (!b->tri()) throw HipError("not a triangle-method chain batch");
-        HIPCHECK(hipStreamSynchronize(b->stream()));
-        HIPCHECK(hipMemcpy(b->u + (size_t)chain * b->p, u, (size_t)b->p * sizeof(double),
-                           hipMemcpyHostToDevice));
-    });
+    return b->with_chain(chain, b->tri() ? nullptr : "not a triangle-method chain batch",
+                         chain_set_tri_state(u));
 }
 
 int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d) {
@@ -2648,9 +2678,8 @@ int bb_chains_quantiles_get(bb_chains *b, const double *probs, int nprobs, doubl
 unsigned bb_chains_error_flags(bb_chains *b, int chain) {
     g_last_error.clear();
     try {
-        b->check_chain(chain);
         uint32_t f = 0;
-        HIPCHECK(hipMemcpyAsync(&f, b->err + chain, sizeof(f), hipMemcpyDeviceToHost,
+        HIPCHECK(hipMemcpyAsync(&f, b->chain(chain).st.err, sizeof(f), hipMemcpyDeviceToHost,
                                 b->stream()));
         HIPCHECK(hipStreamSynchronize(b->stream()));
         return f;
@@ -3045,6 +3074,17 @@ int chain_devices(const bb_config &c, int nvis = -1) {
     return std::max(1, k);
 }
 
+// "Error: <message>" and the line the reference's samplers end on after an error
+__attribute__((format(printf, 1, 2))) void print_abort(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    printf("Error: ");
+    vprintf(fmt, ap);
+    va_end(ap);
+    printf("\nAborting Gibbs sampler.\n");
+    fflush(stdout);
+}
+
 // One chain: a single engine, or the column shards of a multi-device RCCL group.
 struct Chain {
     std::vector<bb_engine *> eng;
@@ -3058,9 +3098,8 @@ struct Chain {
         for (auto *e : eng) bb_engine_destroy(e);
     }
     int init() { return grp ? bb_group_init_state(grp) : bb_engine_init_state(eng[0]); }
-    bool fused() const { return !grp && eng.size() == 1 && eng[0]->fused; }
-    // sweeps per launch (and per interrupt poll) of a .C call
-    int block() const { return !fused() ? 10 : eng[0]->wide ? kWideBlock : 50; }
+    // sweeps per launch (and per interrupt poll) of a .C call: column shards are never fused
+    int block() const { return eng[0]->path.block(); }
     int run(uint64_t t0, int count, int slot, int step, int mcmc) {
         return grp ? bb_group_run(grp, t0, count, slot, step, mcmc)
                    : bb_engine_run(eng[0], t0, count, slot, step, mcmc);
@@ -3075,6 +3114,11 @@ struct Chain {
         }
         return all;
     }
+    // the numerical failures of a complete run, as the drivers print them
+    void report_flags() {
+        const uint32_t f = flags();
+        if (f & ~4u) print_abort("numerical failure in the device sampler (flags %u)", f);
+    }
     // Marks the work enqueued so far (member 0's stream: members advance in lockstep through
     // the exchanges) and waits until at most two marked blocks are ahead of the device.
     void throttle() {
@@ -3085,14 +3129,11 @@ struct Chain {
     int copy_out(int slot0, int count, int s0, const Traces &o) {
         if (count <= 0) return 0;
         const size_t P = (size_t)p;
-        if (eng.size() == 1) {
-            int rc = bb_engine_get_trace(eng[0], slot0, count, o.beta + s0 * P, o.lam + s0 * P,
-                                         o.sig2 ? o.sig2 + s0 : nullptr, o.tau + s0, o.alpha + s0);
-            if (rc == 0 && (o.u || o.shape))
-                rc = bb_engine_get_tri_trace(eng[0], slot0, count, o.u ? o.u + s0 * P : nullptr,
-                                             o.shape ? o.shape + s0 * P : nullptr);
-            return rc;
-        }
+        if (eng.size() == 1)  // the batch's copy with one chain
+            return guarded([&] {
+                HIPCHECK(hipStreamSynchronize(eng[0]->stream));
+                chain_copy_out(eng[0]->view(), 1, slot0, count, s0, 0, o);
+            });
         for (size_t r = 0; r < eng.size(); ++r) {
             bb_engine *e = eng[r];
             const size_t pl = (size_t)e->p_loc;
@@ -3205,34 +3246,6 @@ Outcome drive_schedule(C &ch, int kBlock, int nburn, uint64_t t_base, int m, int
     return OUT_OK;
 }
 
-// "Error: <message>" and the line the reference's samplers end on after an error
-__attribute__((format(printf, 1, 2))) void print_abort(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    printf("Error: ");
-    vprintf(fmt, ap);
-    va_end(ap);
-    printf("\nAborting Gibbs sampler.\n");
-    fflush(stdout);
-}
-
-Outcome drive_chain(Chain &ch, int nburn, uint64_t t_base, int m, int b, const Traces &out,
-                    double *runtime) {
-    // BridgeWrapper.cpp:273-275, 295-297 poll every 10 sweeps.  A fused engine runs a
-    // whole block in one launch at ~15-30 us per sweep, so it polls every 50 (< 2 ms) and
-    // pays the launch and LDS-staging prologue once per 50 sweeps instead of per 10.
-    // The wide fused kernel's sweeps are ~100 us: kWideBlock of them keep the poll near the
-    // general path's 10 sweeps in time.
-    const int kBlock = ch.block();
-    return drive_schedule(
-        ch, kBlock, nburn, t_base, m, b, runtime,
-        [&](int slot0, int count, int s0) { return ch.copy_out(slot0, count, s0, out); },
-        [&] {
-            const uint32_t f = ch.flags();
-            if (f & ~4u) print_abort("numerical failure in the device sampler (flags %u)", f);
-        });
-}
-
 void print_banner(const char *title, const bb_config &c, int b, int m) {
     if (!g_verbose) return;  // BridgeWrapper.cpp:235-240 (stable), :112-117 (triangles)
     printf("%s", title);
@@ -3260,42 +3273,53 @@ CallKind tri_kind(int b) {
     return {"Bridge Regression (mix. of triangles):", 4, b, (uint64_t)b};
 }
 
+// The frame of every .C sampler call: the banner, `run` (whatever it builds is gone when it
+// returns), bb_last_error and the reference's closing line after an error, else the completion
+// line -- "of K chains" for a batch (K > 0) -- and the interrupt flag of bb_last_call_info.
+template <class Run>
+Outcome call_frame(const CallKind &kd, const bb_config &c, int b, int K, double *runtime,
+                   Run run) {
+    const int m = c.trace_capacity;
+    print_banner(kd.title, c, b, m);
+    g_last_interrupted = 0;
+    *runtime = 0.0;
+    const Outcome o = run();
+    if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
+    if (g_verbose && o == OUT_OK) {
+        printf("Sampling complete: %g sec. for %i iterations", *runtime, m);
+        K > 0 ? printf(" of %i chains.\n", K) : printf(".\n");
+    }
+    g_last_interrupted = o == OUT_INTERRUPTED;
+    return o;
+}
+
 // One chain of a .C sampler call over the engines `create` makes.  Errors print and return
 // partial traces.
 template <class Create>
 Outcome sampler_call(const CallKind &kd, const bb_config &c, int b, Create create,
                      const Traces &out, double *runtime) {
-    const int m = c.trace_capacity;
-    print_banner(kd.title, c, b, m);
-    g_last_interrupted = 0;
-    Outcome o;
-    {
+    return call_frame(kd, c, b, 0, runtime, [&] {
         Chain ch;
-        if (chain_build(ch, c, kd.ntr, create) != 0) {
-            print_abort("%s", g_last_error.c_str());
-            *runtime = 0.0;
-            return OUT_ERROR;
-        }
+        if (chain_build(ch, c, kd.ntr, create) != 0) return OUT_ERROR;
         g_last_devices = (int)ch.eng.size();
         g_last_capacity = ch.cap;
-        o = drive_chain(ch, kd.nburn, kd.t_base, m, b, out, runtime);
-        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
-    }
-    if (g_verbose && o == OUT_OK) printf("Sampling complete: %g sec. for %i iterations.\n", *runtime, m);
-    g_last_interrupted = o == OUT_INTERRUPTED;
-    return o;
+        return drive_schedule(
+            ch, ch.block(), kd.nburn, kd.t_base, c.trace_capacity, b, runtime,
+            [&](int slot0, int count, int s0) { return ch.copy_out(slot0, count, s0, out); },
+            [&] { ch.report_flags(); });
+    });
 }
 
-// ... over a dense column-major X (a shard takes its columns)
+// the engines of a dense column-major X with n rows (a shard takes its columns)
+auto dense_create(const double *yp, const double *Xp, int n) {
+    return [=](const bb_config *cc, int j0, int, bb_engine **e) {
+        return bb_engine_create(cc, Xp + (size_t)j0 * n, yp, e);
+    };
+}
+// ... over such an X
 Outcome dense_call(const CallKind &kd, const bb_config &c, const double *yp, const double *Xp,
                    int b, const Traces &out, double *runtime) {
-    const int n = c.n;
-    return sampler_call(
-        kd, c, b,
-        [&](const bb_config *cc, int j0, int, bb_engine **e) {
-            return bb_engine_create(cc, Xp + (size_t)j0 * n, yp, e);
-        },
-        out, runtime);
+    return sampler_call(kd, c, b, dense_create(yp, Xp, c.n), out, runtime);
 }
 
 // A chain batch as drive_schedule drives it: every run advances all K chains.
@@ -3307,41 +3331,39 @@ struct ChainsRun {
         return bb_chains_run(b, t0, count, slot, step, mcmc);
     }
     int sync() { return bb_chains_sync(b); }
-    void throttle() { b->throttle(); }
+    void throttle() { b->ahead.mark(b->stream()); }
 };
 
-// K chains of a small design as one batch on drive_chain's schedule (the blocks of a fused
-// single chain: 50 sweeps, kWideBlock on the wide kernel).  The trace budget bounds the batch:
-// each chain's ring gets a K-th.
+// K chains of a small design as one batch on drive_schedule, in ChainPath::block()'s blocks.
+// The trace budget bounds the batch: each chain's ring gets a K-th.
 // With `sum` the ring fills are not copied out but reduced on the device behind the sweeps
 // (bb_chains::summary_add), and the summaries come back after a complete run.
 Outcome chains_batch(const CallKind &kd, const bb_config &c0, int K, const double *yp,
                      const double *Xp, int b, const Traces &out, double *runtime,
                      const SummaryOut *sum = nullptr) {
     const int m = c0.trace_capacity;
-    *runtime = 0.0;
     bb_config c = c0;
     c.trace_capacity = ring_capacity(m, c.p, kd.ntr, K);
     bb_chains *raw = nullptr;
     if (bb_chains_create(&c, K, Xp, yp, &raw) != 0) return OUT_ERROR;
     std::unique_ptr<bb_chains> ch(raw);
     g_last_devices = 1;
-    g_last_capacity = ch->cap;
-    ChainsRun run{raw, ch->cap};
+    g_last_capacity = ch->v.cap;
+    ChainsRun run{raw, ch->v.cap};
     if (sum && bb_chains_summary_reset(raw, m, sum->maxlag) != 0) return OUT_ERROR;
     if (sum && sum->quant && bb_chains_quantiles_reset(raw) != 0) return OUT_ERROR;
     const Outcome o = drive_schedule(
-        run, ch->block(), kd.nburn, kd.t_base, m, b, runtime,
+        run, ch->path.block(), kd.nburn, kd.t_base, m, b, runtime,
         [&](int slot0, int count, int s0) {
             if (sum)
                 ch->summary_add(slot0, count, s0);
             else
-                ch->copy_out(slot0, count, s0, m, out);
+                chain_copy_out(ch->v, K, slot0, count, s0, m, out);
             return 0;
         },
         [&] {
             std::vector<uint32_t> f(K, 0u);
-            HIPCHECK(hipMemcpy(f.data(), ch->err, (size_t)K * sizeof(uint32_t),
+            HIPCHECK(hipMemcpy(f.data(), ch->v.st.err, (size_t)K * sizeof(uint32_t),
                                hipMemcpyDeviceToHost));
             for (int k = 0; k < K; ++k)
                 if (f[k] & ~4u)
@@ -3366,16 +3388,9 @@ Outcome chains_call(const CallKind &kd, const bb_config &c, int K, const double 
                     const double *Xp, int b, const Traces &out, double *runtime) {
     const int m = c.trace_capacity;
     *runtime = 0.0;
-    if (chains_refusal(c) == nullptr) {
-        print_banner(kd.title, c, b, m);
-        g_last_interrupted = 0;
-        const Outcome o = chains_batch(kd, c, K, yp, Xp, b, out, runtime);
-        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
-        if (g_verbose && o == OUT_OK)
-            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime, m, K);
-        g_last_interrupted = o == OUT_INTERRUPTED;
-        return o;
-    }
+    if (chain_plan(c, true).kind != CK_NONE)
+        return call_frame(kd, c, b, K, runtime,
+                          [&] { return chains_batch(kd, c, K, yp, Xp, b, out, runtime); });
     for (int k = 0; k < K; ++k) {
         bb_config ck = c;
         ck.stream = c.stream + (uint64_t)k;
@@ -3395,60 +3410,40 @@ Outcome chains_call(const CallKind &kd, const bb_config &c, int K, const double 
 Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const double *yp,
                            const double *Xp, const SummaryOut &out, double *runtime,
                            TraceQuantiles *tq = nullptr, int nchains = 1) {
-    const int m = c.trace_capacity, n = c.n;
-    print_banner(kd.title, c, b, m);
-    g_last_interrupted = 0;
-    *runtime = 0.0;
-    Outcome o;
-    {
+    const int m = c.trace_capacity;
+    return call_frame(kd, c, b, 0, runtime, [&] {
         Chain ch;
-        if (chain_build(ch, c, kd.ntr,
-                        [&](const bb_config *cc, int j0, int, bb_engine **e) {
-                            return bb_engine_create(cc, Xp + (size_t)j0 * n, yp, e);
-                        }) != 0 ||
-            ch.eng.size() != 1) {
+        if (chain_build(ch, c, kd.ntr, dense_create(yp, Xp, c.n)) != 0 || ch.eng.size() != 1) {
             if (ch.eng.size() > 1) set_error("summaries need every column on one device");
-            print_abort("%s", g_last_error.c_str());
             return OUT_ERROR;
         }
         g_last_devices = 1;
         g_last_capacity = ch.cap;
         bb_engine *e = ch.eng[0];
         TraceSummary ts;
-        const SummaryRing ring{.beta = e->tr_beta, .sig2 = e->tr_sig2, .tau = e->tr_tau,
-                               .alpha = e->tr_alpha, .p = e->p_loc, .cap = ch.cap};
-        o = (Outcome)guarded(e->cfg.device, [&] {
-            ts.reset(e->stream, 1, c.p + 3, m, out.maxlag);
-            if (tq && !tq->ready()) tq->reset(e->stream, nchains, c.p + 3, m);
-            return (int)OUT_OK;
-        });
-        if (o != OUT_OK) o = OUT_ERROR;
-        if (o == OUT_OK)
-            o = drive_schedule(
-                ch, ch.block(), kd.nburn, kd.t_base, m, b, runtime,
-                [&](int slot0, int count, int s0) {
-                    HIPCHECK(hipSetDevice(e->cfg.device));
-                    ts.add(e->stream, ring, slot0, count, s0);
-                    if (tq) tq->add(e->stream, ring, 1, slot0, count, s0);
-                    return 0;
-                },
-                [&] {
-                    const uint32_t f = ch.flags();
-                    if (f & ~4u)
-                        print_abort("numerical failure in the device sampler (flags %u)", f);
-                });
+        const SummaryRing ring = e->view().ring();
+        if (guarded(e->cfg.device, [&] {
+                ts.reset(e->stream, 1, c.p + 3, m, out.maxlag);
+                if (tq && !tq->ready()) tq->reset(e->stream, nchains, c.p + 3, m);
+            }) != 0)
+            return OUT_ERROR;
+        const Outcome o = drive_schedule(
+            ch, ch.block(), kd.nburn, kd.t_base, m, b, runtime,
+            [&](int slot0, int count, int s0) {
+                HIPCHECK(hipSetDevice(e->cfg.device));
+                ts.add(e->stream, ring, slot0, count, s0);
+                if (tq) tq->add(e->stream, ring, 1, slot0, count, s0);
+                return 0;
+            },
+            [&] { ch.report_flags(); });
         if (o == OUT_OK &&
             guarded(e->cfg.device, [&] {
                 ts.get(e->stream, out.mean, out.var, out.acov, out.hmean, out.hvar);
                 *out.flags = (int)ch.flags();
             }) != 0)
-            o = OUT_ERROR;
-        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
-    }
-    if (g_verbose && o == OUT_OK)
-        printf("Sampling complete: %g sec. for %i iterations.\n", *runtime, m);
-    g_last_interrupted = o == OUT_INTERRUPTED;
-    return o;
+            return OUT_ERROR;
+        return o;
+    });
 }
 
 // bridge_reg_stable_chains_summary / bridge_regression_chains_summary: chains_call with the
@@ -3457,18 +3452,11 @@ Outcome summary_chain_call(const CallKind &kd, const bb_config &c, int b, const 
 Outcome chains_summary_call(const char *entry, const CallKind &kd, const bb_config &c, int K,
                             const double *yp, const double *Xp, int b, const SummaryOut &out,
                             double *runtime) {
-    const int m = c.trace_capacity;
     *runtime = 0.0;
-    if (chains_refusal(c) == nullptr) {
-        print_banner(kd.title, c, b, m);
-        g_last_interrupted = 0;
-        const Outcome o = chains_batch(kd, c, K, yp, Xp, b, Traces{}, runtime, &out);
-        if (o == OUT_ERROR) print_abort("%s", g_last_error.c_str());
-        if (g_verbose && o == OUT_OK)
-            printf("Sampling complete: %g sec. for %i iterations of %i chains.\n", *runtime, m, K);
-        g_last_interrupted = o == OUT_INTERRUPTED;
-        return o;
-    }
+    if (chain_plan(c, true).kind != CK_NONE)
+        return call_frame(kd, c, b, K, runtime, [&] {
+            return chains_batch(kd, c, K, yp, Xp, b, Traces{}, runtime, &out);
+        });
     if (const int ndev = chain_devices(c); ndev > 1) {
         set_error("%s: this design would be sharded by columns over %d devices; summaries need "
                   "every column on one device (bb_set_device_count(1))", entry, ndev);
@@ -3530,6 +3518,11 @@ Outcome stable_csc(const bb_config &c, const double *yp, const int *Xcolptr, con
     return dense_call(stable_kind(b), c, yp, Xd.data(), b, out, runtime);
 }
 
+// the logistic family: the stable driver's schedule under its own banner
+CallKind logit_kind(int b) {
+    return stable_kind(b, "Bridge Regression (logistic, Polya-Gamma mix. of normals):");
+}
+
 Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, Traces out,
                    double *runtime) {
     c.method = LOGIT;
@@ -3541,14 +3534,7 @@ Outcome logit_call(bb_config c, const double *yp, const double *Xp, int b, Trace
         }
     std::vector<double> sig2(c.trace_capacity);
     out.sig2 = sig2.data();
-    return dense_call(
-        stable_kind(b, "Bridge Regression (logistic, Polya-Gamma mix. of normals):"), c, yp, Xp,
-        b, out, runtime);
-}
-
-// the logistic family: the stable driver's schedule under its own banner
-CallKind logit_kind(int b) {
-    return stable_kind(b, "Bridge Regression (logistic, Polya-Gamma mix. of normals):");
+    return dense_call(logit_kind(b), c, yp, Xp, b, out, runtime);
 }
 
 // a logistic entry's y, checked before a key is taken or an output is touched

@@ -346,6 +346,15 @@ int bb_chains_get_tri_basis(bb_chains *b, double *tV, double *a, double *d);
 int bb_chains_get_omega(bb_chains *b, int chain, double *omega);
 int bb_chains_threads(const bb_chains *b);
 int bb_chains_set_threads(bb_chains *b, int threads);
+/* The fused chain kernel family that a bb_engine (batch == 0) or a chain batch (batch != 0)
+ * created now from cfg runs, by the rules above and the current bb_set_tuning keys 25, 26, 27:
+ * 0 none (the general path), 1 small, 2 wide, 3 triangle, 4 logistic.  For a batch 0 is a
+ * refusal, and bb_last_error holds bb_chains_create's text without its "bb_chains_create: "
+ * prefix (it is empty otherwise).  Reads cfg alone, needs no device.  The batch differs from the
+ * engine in three ways: it requires p_local == p; it takes methods 0, 1, 4 and 6 alone, where an
+ * engine with `ortho` set runs the orthogonal draw fused under methods 2, 3 and 5 too; and only
+ * it has a logistic kernel.  (A design given in CSC form never runs fused.) */
+int bb_chain_kernel(const bb_config *cfg, int batch);
 
 /*
  * K independent chains of bridge_reg_stable in one call: the arguments of bridge_reg_stable

@@ -48,7 +48,7 @@ def test_shape_refusals_have_their_own_messages():
 
 
 def test_accepted_shape_is_not_refused_for_its_shape():
-    """p = 32, n = 40 passes chains_refusal (alpha known or unknown); without a device the
+    """p = 32, n = 40 passes the batch rules of chain_plan (alpha known or unknown); without a device the
     creation fails later, with another message."""
     for kw in ({}, dict(true_alpha=0.0)):
         msg = create_error(40, 32, **kw)

@@ -67,7 +67,7 @@ EXPORTED_SYMBOLS = [
     "rtexpon_rate", "mytest", "bb_trunc_batch", "rrtgamma_rate", "bb_rrtgamma_batch",
     "bridge_reg_stable_csc", "bb_engine_create_csc", "bb_engine_sparse_pairs", "bb_sparse_gram",
     "bb_bench_sparse_gram", "bb_engine_sparse_info", "bridge_reg_logit", "bb_engine_get_omega",
-    "bb_pg_batch", "bb_group_create_rccl", "bb_group_sync", "bb_set_device_count",
+    "bb_pg_batch", "bb_gamma_batch", "bb_group_create_rccl", "bb_group_sync", "bb_set_device_count",
     "bb_set_trace_budget", "bb_debug_interrupt_after", "bb_last_call_info",
     "bb_engine_set_timed_phase", "bb_engine_set_timing_stride", "bb_set_chol_version",
     "bb_set_tuning", "bridge_reg_stable_chains", "bb_chains_create", "bb_chains_destroy",
@@ -200,6 +200,7 @@ def library(build: bool = True) -> ctypes.CDLL:
                                                   [_ip] * 4 + [_dp, _ip])
     L.bb_chains_get_omega.argtypes = [c.c_void_p, c.c_int, _dp]
     L.bb_pg_batch.argtypes = [_dp, _dp, c.c_int, c.c_uint64, c.c_uint64, c.c_uint64]
+    L.bb_gamma_batch.argtypes = [_dp, _dp, c.c_int, c.c_uint64, c.c_uint64, c.c_uint64]
     L.bb_engine_sparse_info.argtypes = [c.c_void_p, c.POINTER(c.c_longlong),
                                         c.POINTER(c.c_longlong), _ip, _ip]
     L.bb_sparse_gram.argtypes = [_dp, _dp, _ip, _ip, _dp, _dp, _dp, c.c_int, c.c_int]
@@ -981,6 +982,18 @@ def pg_batch(psi, seed, stream=0, t=0):
     om = np.zeros_like(psi)
     _check(L.bb_pg_batch(_p(om), _p(psi), psi.shape[0], seed, stream, t), "bb_pg_batch")
     return om
+
+
+def gamma_batch(shape, seed, stream=0, t0=0):
+    """x_i ~ Ga(shape_i, 1) on the device under an explicit key: the engines' gamma sampler,
+    draw i on sweep counter t0 + i with the tau step's kind (tests)."""
+    L = library()
+    _require_gpu()
+    shape = np.ascontiguousarray(shape, dtype=np.float64)
+    x = np.zeros_like(shape)
+    _check(L.bb_gamma_batch(_p(x), _p(shape), shape.shape[0], seed, stream, t0),
+           "bb_gamma_batch")
+    return x
 
 
 def _dotC(name, num, *params):

@@ -456,6 +456,10 @@ void launch_rrtgamma_batch(hipStream_t s, int num, double *x, const double *shap
 void launch_pg(hipStream_t s, const double *psi, int n, int n_pad, uint64_t k0, uint64_t k1,
                uint64_t t, double *omega, uint32_t *err);
 void launch_kappa(hipStream_t s, const double *y, int n, int n_pad, double *kappa);
+// x_i ~ Ga(shape_i, 1) by gamma1 on sweep counter t0 + i, kind KIND_TAU (tests); err bit 1
+// when a draw exhausted its attempts.
+void launch_gamma_batch(hipStream_t s, const double *shape, int num, uint64_t k0, uint64_t k1,
+                        uint64_t t0, double *x, uint32_t *err);
 
 // The arguments of the fused chain launchers by role, each filled with designated
 // initialisers (a transposed pair of pointers does not compile silently).

@@ -29,6 +29,22 @@ void launch_pg(hipStream_t s, const double *psi, int n, int n_pad, uint64_t k0, 
     k_pg<<<(n_pad + 255) / 256, 256, 0, s>>>(psi, n, n_pad, Key{k0, k1}, t, omega, err);
 }
 
+// x_i ~ Ga(shape_i, 1): gamma1 (bb_sampler.h) unchanged, draw i on sweep counter t0 + i with
+// the tau step's kind -- gamma1 has one draw per (key, t, kind).  A probe for the tests: in
+// the engines gamma1 is only seen through whole chains.
+__global__ __launch_bounds__(256) void k_gamma_batch(const double *__restrict__ shape, int num,
+                                                     Key key, uint64_t t0,
+                                                     double *__restrict__ x, uint32_t *err) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < num) x[i] = gamma1(shape[i], key, t0 + (uint64_t)i, KIND_TAU, err);
+}
+
+void launch_gamma_batch(hipStream_t s, const double *shape, int num, uint64_t k0, uint64_t k1,
+                        uint64_t t0, double *x, uint32_t *err) {
+    if (num <= 0) return;
+    k_gamma_batch<<<(num + 255) / 256, 256, 0, s>>>(shape, num, Key{k0, k1}, t0, x, err);
+}
+
 // kappa_i = y_i - 1/2 (0 on padding rows)
 __global__ void k_kappa(const double *y, int n, int n_pad, double *kappa) {
     const int i = blockIdx.x * 256 + threadIdx.x;

@@ -62,6 +62,27 @@ int bb_pg_batch(double *omega, const double *psi, int n, uint64_t seed, uint64_t
     });
 }
 
+int bb_gamma_batch(double *x, const double *shape, int num, uint64_t seed, uint64_t stream,
+                   uint64_t t0) {
+    if (num <= 0) return 0;
+    return guarded(g_device, [&] {
+        Scratch dev;
+        double *da = dev.alloc<double>(num), *dx = dev.alloc<double>(num);
+        uint32_t *de = dev.alloc<uint32_t>(1);
+        HIPCHECK(hipMemcpy(da, shape, (size_t)num * sizeof(double), hipMemcpyHostToDevice));
+        launch_gamma_batch(0, da, num, seed, stream, t0, dx, de);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(x, dx, (size_t)num * sizeof(double), hipMemcpyDeviceToHost));
+        uint32_t f = 0;
+        HIPCHECK(hipMemcpy(&f, de, sizeof(f), hipMemcpyDeviceToHost));
+        if (f) {
+            set_error("gamma: rejection cap reached (flags %u)", f);
+            return -2;
+        }
+        return 0;
+    });
+}
+
 int bb_trunc_batch(int mode, int num, double *x, const double *p0, const double *p1,
                    const double *p2, const double *p3, uint64_t seed, uint64_t stream) {
     if (num <= 0) return 0;

@@ -587,6 +587,12 @@ int bb_trunc_batch(int mode, int num, double *x, const double *p0, const double 
 int bb_pg_batch(double *omega, const double *psi, int n, uint64_t seed, uint64_t stream,
                 uint64_t t);
 
+/* x_i ~ Ga(shape_i, rate 1), i < num, under key (seed, stream): draw i is the engines' gamma
+ * sampler (Marsaglia-Tsang, the one behind every tau and sig2 step) on sweep counter t0 + i
+ * with the tau step's counter kind (tests).  Returns 0, or -2 if a draw failed. */
+int bb_gamma_batch(double *x, const double *shape, int num, uint64_t seed, uint64_t stream,
+                   uint64_t t0);
+
 /* rrtgamma_rate under an explicit key (seed, stream). */
 int bb_rrtgamma_batch(int num, double *x, const double *shape, const double *rate,
                       const double *right_t, uint64_t seed, uint64_t stream);

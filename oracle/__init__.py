@@ -78,6 +78,8 @@ def lib():
                                         ctypes.c_uint64, _lp]
         L.bbo_gamma1.argtypes = [ctypes.c_double, _u64p, ctypes.c_uint64, ctypes.c_uint]
         L.bbo_gamma1.restype = ctypes.c_double
+        L.bbo_gamma_batch.argtypes = [_dp, _dp, ctypes.c_long, _u64p, ctypes.c_uint64]
+        L.bbo_gamma_batch.restype = None
         L.bbo_tau_from_sum.argtypes = [ctypes.c_double, ctypes.c_long, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, _u64p, ctypes.c_uint64]
         L.bbo_tau_from_sum.restype = ctypes.c_double
@@ -210,6 +212,15 @@ def sample_lambda(beta, alpha, tau, seed, stream, t, j0=0):
 
 def gamma1(shape, seed, stream, t, kind):
     return lib().bbo_gamma1(shape, _key(seed, stream), t, kind)
+
+
+def gamma_batch(shape, seed, stream=0, t0=0):
+    """x_i ~ Ga(shape_i, 1): ``gamma1`` on sweep counter t0 + i with the tau step's kind
+    (bb_oracle.c bbo_gamma_batch), the oracle of ``bayesbridge_amd.gamma_batch``."""
+    shape = np.ascontiguousarray(shape, dtype=np.float64)
+    x = np.empty_like(shape)
+    lib().bbo_gamma_batch(_ptr(x), _ptr(shape), shape.shape[0], _key(seed, stream), t0)
+    return x
 
 
 def sum_abs_pow(beta, alpha):

@@ -359,6 +359,13 @@ double bbo_gamma1(double shape, const uint64_t key[2], uint64_t t, unsigned kind
     }
 }
 
+/* x_i ~ Ga(shape_i, 1), draw i on sweep counter t0 + i with the tau step's kind (3): bbo_gamma1
+ * has one draw per (key, t, kind).  Mirrors the device probe bb_gamma_batch. */
+void bbo_gamma_batch(double *x, const double *shape, long num, const uint64_t key[2], uint64_t t0)
+{
+    for (long i = 0; i < num; ++i) x[i] = bbo_gamma1(shape[i], key, t0 + (uint64_t)i, 3);
+}
+
 /* BridgeRegression.cpp:453-465: nu ~ Ga(nu_shape + p/alpha, rate = nu_rate + sum|b|^a). */
 double bbo_tau_from_sum(double sum_abs_pow, long p, double alpha, double nu_shape, double nu_rate,
                         const uint64_t key[2], uint64_t t)

@@ -1,7 +1,8 @@
 """CPU tests of the truncated-distribution utilities (BridgeWrapper.cpp:738-935): the
 oracle restatement against scipy (the reference's RNG library is un-vendored, so these
-draws are pinned distributionally), the rtnorm / rtexpon_rate special-value rules, and
-the host-only mytest marshalling check through the C ABI."""
+draws are pinned distributionally; tests/test_sampler_law_cpu.py holds them to their exact
+laws at the branch edges), the rtnorm / rtexpon_rate special-value rules, and the host-only
+mytest marshalling check through the C ABI."""
 import ctypes
 import struct
 
